@@ -11,15 +11,27 @@ boards, and the step's outputs (action played, reward, done, reason) of every bo
 to a per-ply trace in HBM.  The K timed steps are ONE launch of the fused rollout kernel
 k_env_rollout4 (four waves per 64 boards; gc_env_rollout_device: the state stays in registers between plies; every
 ply's window probe / commit and outputs go through HBM).  State, repetition windows and
-outputs stay in HBM; nothing crosses PCIe in the timed region.  The launched form (one
-kernel launch per ply, k_env_step2 over two board-range streams) is timed beside it as
-"launched_step".
+outputs stay in HBM; nothing crosses PCIe in the timed region.
+
+A plain run does only what that headline needs: set up, settle, warm up, time the K steps,
+print the line.  --full adds every other leg to the same line, each with its own switch: the
+launched form (one kernel launch per ply, k_env_step2 over two board-range streams, timed as
+"launched_step"), the API-shaped step, the env variants, the single-board env, both perft
+configs with their oracle and fixture checks, the replicas' common-interval leg, the CPU
+baselines, and the trace / step-counter cross-check of the timed region.
+
+--dump-outputs DIR writes what the timed launch handed its caller in its last step, as
+DIR/<name>.npy (float32, [boards] or [boards, k], replicas of this process concatenated):
+action, reward, done, reason (the last ply's row of the trace) and boards, meta, nsteps (the
+envs' state and step counters right after the launch).  Boards, seeds and the policy's Philox
+streams are functions of the arguments alone, so two builds run with the same arguments can be
+compared array by array.
 
 The batch is first settled into steady state (a fused rollout of --settle plies, then
 --warmup steps), so the timed steps see mid/late-game boards, resets and terminals in their
 steady-state proportions, whatever --warmup is.
 
-  python bench.py [--gpus N --steps K --warmup W --boards B]
+  python bench.py [--gpus N --steps K --warmup W --boards B] [--full] [--dump-outputs DIR]
       N replicas in ONE process: one host thread + one env handle per device (no torch)
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
       one process per GPU; barrier / max / sum through a file group (gym_chess_amd.replicas)
@@ -84,6 +96,11 @@ def parse():
                     help="fused-rollout plies before --warmup: moves the batch from all-startpos into steady state")
     ap.add_argument("--boards", type=int, default=65536)
     ap.add_argument("--seed", type=int, default=0x5EED + 3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (launched / API / variant / single-env steps, perft configs and "
+                         "their checks, the replicas' common interval, CPU baselines); the switches below apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed launch's last-step outputs and the envs' state after it to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-boards", type=int, default=32768)
     ap.add_argument("--cpu-sample-plies", type=int, default=300)
@@ -98,7 +115,8 @@ def parse():
     ap.add_argument("--single-episodes", type=int, default=10,
                     help="configs[0]: the reference benchmark driver on the single-board env (0 = skip)")
     ap.add_argument("--concurrent-ms", type=float, default=0.0,
-                    help="replicas' common-interval leg (>= this many ms per replica); always on (250 ms) for N > 1")
+                    help="replicas' common-interval leg (>= this many ms per replica); with --full always on "
+                         "(250 ms) for N > 1")
     ap.add_argument("--configs1-roots", type=int, default=4096,
                     help="configs[1]: start-position roots of the perft(3) leg (0 = skip)")
     ap.add_argument("--perft-depth", type=int, default=5)
@@ -340,7 +358,8 @@ def perft_startpos_leg(args, rep, depth=3, reps=20):
     return out
 
 
-PERFT_FIXTURE = os.path.join(ROOT, "tests", "golden", "configs3_perft.npz")
+PERFT_FIXTURE = os.path.join(ROOT, "tests", "golden", "configs3_perft_counts.npz")
+PERFT_FIXTURE_BOARDS = [os.path.join(ROOT, "tests", "golden", f"configs3_perft_boards{h}.npz") for h in (0, 1)]
 
 
 def fixture_check(args, rep, ctx0, nodes):
@@ -355,8 +374,9 @@ def fixture_check(args, rep, ctx0, nodes):
         return None
     eng, b, m = ctx0
     f = np.load(PERFT_FIXTURE)
-    same = bool((b == f["boards"]).all() and (m[:, :7] == f["metas"][:, :7]).all())
-    assert same, "the perft roots differ from the fixture's (tests/golden/configs3_perft.npz)"
+    fb = np.concatenate([np.load(p)["boards"] for p in PERFT_FIXTURE_BOARDS])  # the roots, stored in two halves
+    same = bool((b == fb).all() and (m[:, :7] == f["metas"][:, :7]).all())
+    assert same, "the perft roots differ from the fixture's (tests/golden/configs3_perft_*.npz)"
     s5 = f["stride5"]
     bad5 = s5[np.nonzero(nodes[s5] != f["perft5"])[0]]
     assert len(bad5) == 0, f"perft(5) differs from the fixture at roots {bad5[:8]}"
@@ -633,8 +653,67 @@ def launched_leg(args, rep, envs, n):
     return out
 
 
+TRACE_CHUNK = 64  # plies per host copy of a device trace (32 MiB at 65 536 boards)
+
+
+def trace_rows(env, tb, first, k):
+    """host copy of plies [first, first + k) of a device trace: the packed words, uint64 [ply][board]"""
+    import ctypes
+
+    import numpy as np
+
+    from gym_chess_amd import _lib
+
+    w = np.zeros((k, env.num_boards), dtype=np.uint64)
+    if w.size:
+        _lib.check(env._L.gc_env_copy(env._h, _lib.ptr(w), tb.ptr + 8 * first * env.num_boards,
+                                      ctypes.c_uint64(w.nbytes), 2))
+    return w
+
+
+def trace_steps(env, tb, plies):
+    """env.step() calls in the first `plies` plies of a device trace (action -1: the driver's
+    no-move reset, not a step), counted TRACE_CHUNK plies at a time"""
+    import numpy as np
+
+    total = 0
+    for p in range(0, plies, TRACE_CHUNK):
+        w = trace_rows(env, tb, p, min(TRACE_CHUNK, plies - p))
+        total += int(((w & np.uint64(0xFFFF)) != np.uint64(0xFFFF)).sum())
+    return total
+
+
+def dump_outputs(path, ctx, outs, steps):
+    """--dump-outputs: the last timed step's outputs of every board (the last ply's row of the
+    trace the launch filled) and the envs' state right after the launch, as float32 .npy files;
+    this process's replicas concatenated along the board axis.  Every value is a small integer
+    (actions < 4101, rewards, flags, piece ids, step counters < 2^24): exact in float32."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    cols = {k: [] for k in ("action", "reward", "done", "reason", "boards", "meta", "nsteps")}
+    for (env, tb, *_), o in zip(ctx, outs):
+        w = trace_rows(env, tb, steps - 1, 1)[0]
+        cols["action"].append((w & np.uint64(0xFFFF)).astype(np.uint16).view(np.int16))
+        cols["reward"].append(((w >> np.uint64(16)) & np.uint64(0xFFFF)).astype(np.uint16).view(np.int16))
+        cols["done"].append((w >> np.uint64(32)) & np.uint64(0xFF))
+        cols["reason"].append((w >> np.uint64(40)) & np.uint64(0xFF))
+        b, m = env.boards()
+        cols["boards"].append(b)
+        cols["meta"].append(m)
+        cols["nsteps"].append(o["nsteps"])
+    for k, v in cols.items():
+        np.save(os.path.join(path, k + ".npy"), np.concatenate(v).astype(np.float32))
+
+
 def main():
     args = parse()
+    if not args.full:  # a plain run: the headline's steps only
+        args.launched_steps = args.api_steps = args.configs1_roots = args.single_episodes = 0
+        args.variant_steps = args.perft_roots = 0
+        args.no_cpu_baseline = True
+    import numpy as np
+
     from gym_chess_amd.env import BatchedChessEnv
     from gym_chess_amd.replicas import Replicas
 
@@ -678,20 +757,26 @@ def main():
     dt_synced = rep.max(max(synced))
     region_overlap = rep.last_overlap
     kern_ms = [e.elapsed_ms(0, 1) for e in envs]
-    s1 = [int(e.outputs()["nsteps"].sum()) for e in envs]
+    outs = [e.outputs() for e in envs]
+    s1 = [int(o["nsteps"].sum()) for o in outs]
     w1 = [e.window_sum() for e in envs]
-    # env.step() calls in the timed region, from its per-step trace (action -1: the driver's
-    # no-move reset, not a step), cross-checked against the env's step counters, which also
-    # count the warmup's steps
+    # env.step() calls in the timed region: the env's step counters, which also count the
+    # warmup's steps, less the warmup's own, counted from its per-step trace (action -1: the
+    # driver's no-move reset, not a step) -- a host copy of W plies, never of the K timed ones.
+    # --full counts the timed region's trace as well and holds the two against each other.
     steps_local = 0
     for (env, tb, tbw, s0, _), b in zip(ctx, s1):
-        tr = tb.fetch(args.steps)
-        timed = int((tr["action"] != -1).sum())
-        warm = int((tbw.fetch(args.warmup)["action"] != -1).sum()) if args.warmup > 0 else 0
-        assert b - s0 == timed + warm, f"step counters {b - s0} != trace {timed} + {warm}"
-        assert (tr["done"][-1] <= 1).all() and (tr["reason"][-1] <= 10).all()  # the last ply was written
+        warm = trace_steps(env, tbw, args.warmup)
+        timed = b - s0 - warm
+        if args.full:
+            traced = trace_steps(env, tb, args.steps)
+            assert timed == traced, f"step counters {b - s0} != trace {traced} + {warm}"
+        last = trace_rows(env, tb, args.steps - 1, 1)[0]  # the last ply was written
+        assert (((last >> np.uint64(32)) & np.uint64(0xFF)) <= 1).all()
+        assert (((last >> np.uint64(40)) & np.uint64(0xFF)) <= 10).all()
         steps_local += timed
-        del tr
+    if args.dump_outputs and rep.rank == 0:
+        dump_outputs(args.dump_outputs, ctx, outs, args.steps)
     steps_all = rep.sum(steps_local)
     value = steps_all / dt_max
     mean_window = sum(c[4] + w for c, w in zip(ctx, w1)) / (2.0 * n * len(envs))
@@ -729,7 +814,7 @@ def main():
                    "pmc_bytes_vs_alg": (pm.get("bytes_per_board_ply") or 0) / alg if alg else None}
 
     extra = {}
-    if rep.world_size > 1 or args.concurrent_ms > 0:
+    if args.full and (rep.world_size > 1 or args.concurrent_ms > 0):
         extra["concurrent"] = concurrent_leg(args, rep, ctx, n, dt_max / max(args.steps, 1))
     if args.launched_steps > 0:
         extra["launched_step"] = launched_leg(args, rep, envs, n)

@@ -1,4 +1,4 @@
-"""Generate tests/golden/full_width_digests.npz: the oracle's per-board trajectory digests of
+"""Generate tests/golden/full_width_digests_<case>.npz (one file per case): the oracle's per-board trajectory digests of
 65 536 boards x 2 000 plies of random self-play, for the headline driver (opponent "none") and
 the random opponent with a WHITE and with a BLACK agent (long-horizon
 parity at full width, not on a sample).
@@ -22,7 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
-OUT = os.path.join(ROOT, "tests", "golden", "full_width_digests.npz")
+OUT = os.path.join(ROOT, "tests", "golden", "full_width_digests_{}.npz")  # one per case: boards, plies, digest, seed
 BOARDS = 65536
 PLIES = 2000
 # (name, seed, opponent, agent colour)
@@ -36,15 +36,12 @@ def main():
     ap.add_argument("--threads", type=int, default=os.cpu_count() or 1)
     a = ap.parse_args()
     O.build()
-    out = {"boards": np.int64(BOARDS), "plies": np.int64(PLIES)}
     for name, seed, opp, color in CASES:
         t0 = time.time()
-        out[f"{name}_digest"] = O.rollout_digests(seed, BOARDS, PLIES, opponent=opp, agent_white=color == "WHITE",
-                                                  threads=a.threads)
-        out[f"{name}_seed"] = np.int64(seed)
+        d = O.rollout_digests(seed, BOARDS, PLIES, opponent=opp, agent_white=color == "WHITE", threads=a.threads)
         print(f"{name}: {BOARDS} boards x {PLIES} plies, {time.time() - t0:.0f} s", flush=True)
-    np.savez(OUT, **out)
-    print("wrote", OUT)
+        np.savez(OUT.format(name), boards=np.int64(BOARDS), plies=np.int64(PLIES), digest=d, seed=np.int64(seed))
+        print("wrote", OUT.format(name))
 
 
 if __name__ == "__main__":

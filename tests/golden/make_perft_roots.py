@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """configs[3] at full width: the bench's 65 536 mid-game perft roots and their node counts,
 computed by the C oracle (oracle/gc_oracle.c -- test infrastructure), committed as
-tests/golden/configs3_perft.npz.
+tests/golden/configs3_perft_counts.npz and configs3_perft_boards{0,1}.npz (the roots in two
+halves: every committed file stays under 1 MiB); load() reads them back as one dict.
 
 The roots are regenerated exactly as bench.py's `midgame_fens` makes them on the device:
 board i is the position after 10 + (i*7919 mod 31) plies of the random self-play driver
@@ -39,7 +40,16 @@ import oracle as O  # noqa: E402
 N = 65536
 SEED = 0x5EED + 4  # bench.py perft_leg: rp.board_seed(0x5EED + 4), replica 0
 STRIDE5 = 64
-OUT = os.path.join(HERE, "configs3_perft.npz")
+OUT = os.path.join(HERE, "configs3_perft_counts.npz")  # metas, perft4, stride5, perft5
+OUT_BOARDS = [os.path.join(HERE, f"configs3_perft_boards{h}.npz") for h in (0, 1)]  # boards[:N/2], boards[N/2:]
+
+
+def load():
+    """the fixture as one dict of plain arrays (allow_pickle stays False)"""
+    d = np.load(OUT)
+    out = {k: d[k] for k in d.files}
+    out["boards"] = np.concatenate([np.load(f)["boards"] for f in OUT_BOARDS])
+    return out
 
 
 def root_plies(n=N):
@@ -92,7 +102,9 @@ def main():
     s5 = np.arange(0, N, STRIDE5, dtype=np.int64)
     p4 = perft_chunked(boards, metas, 4, args.threads, args.work, "p4")
     p5 = perft_chunked(boards[s5], metas[s5], 5, args.threads, args.work, "p5", chunk=64)
-    np.savez_compressed(OUT, boards=boards, metas=metas, perft4=p4, stride5=s5, perft5=p5)
+    np.savez_compressed(OUT, metas=metas, perft4=p4, stride5=s5, perft5=p5)
+    for h, f in enumerate(OUT_BOARDS):
+        np.savez_compressed(f, boards=boards[h * N // 2:(h + 1) * N // 2])
     print(f"wrote {OUT}: perft4 total {int(p4.sum())}, perft5 stride total {int(p5.sum())}, "
           f"{time.time() - t0:.0f} s", flush=True)
 

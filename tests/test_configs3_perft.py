@@ -1,6 +1,6 @@
 """configs[3] at full width: bench.py's 65 536 mid-game perft roots,
 every root's perft(4) and every 64th root's perft(5) pinned by the oracle
-(tests/golden/configs3_perft.npz, made by tests/golden/make_perft_roots.py: the roots
+(tests/golden/configs3_perft_*.npz, made by tests/golden/make_perft_roots.py: the roots
 regenerated from the oracle's restatement of the random self-play driver, the counts by the
 oracle's perft = lib.rs:460-486 move lists composed with lib.rs:679-784 next_state).
 
@@ -16,14 +16,14 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = os.path.join(ROOT, "tests", "golden", "configs3_perft.npz")
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 
 @pytest.fixture(scope="module")
 def fixture():
-    d = np.load(FIX)  # plain arrays (allow_pickle stays False)
-    return {k: d[k] for k in d.files}
+    import make_perft_roots as M
+
+    return M.load()  # plain arrays (allow_pickle stays False)
 
 
 def test_fixture_shape(fixture):

@@ -76,8 +76,9 @@ def test_multi_device_env_on_one_gpu():
 
 
 def test_bench_threaded_two_replicas_line():
-    """bench.py --gpus 2 in one process on the one GPU (GC_BENCH_DEVICES=0,0): the JSON line
-    reports n_gpus 2, global_boards 2 x boards, replica_mode threads."""
+    """bench.py --full --gpus 2 in one process on the one GPU (GC_BENCH_DEVICES=0,0): the JSON line
+    reports n_gpus 2, global_boards 2 x boards, replica_mode threads (--full: the line carries
+    the replicas' common-interval leg)."""
     import json
     import os
     import subprocess
@@ -87,10 +88,10 @@ def test_bench_threaded_two_replicas_line():
     env = dict(os.environ, GC_BENCH_DEVICES="0,0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup",
-                          "5", "--settle", "300", "--boards", "8192", "--perft-roots", "0", "--variant-steps", "0",
-                          "--no-cpu-baseline", "--launched-steps", "0"], capture_output=True, text=True, env=env,
-                         timeout=300, check=True)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "20",
+                          "--warmup", "5", "--settle", "300", "--boards", "8192", "--perft-roots", "0",
+                          "--variant-steps", "0", "--no-cpu-baseline", "--launched-steps", "0"],
+                         capture_output=True, text=True, env=env, timeout=300, check=True)
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["global_boards"] == 2 * 8192
     assert line["config"]["replica_mode"] == "threads" and line["value"] > 0
@@ -101,8 +102,8 @@ def test_bench_threaded_two_replicas_line():
 
 def test_bench_torchrun_two_ranks_line():
     """The driver's multi-GPU launch shape, rehearsed on the one GPU: python -m
-    torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 (GC_BENCH_DEVICES=0,0 puts both
-    ranks on device 0): one process per rank, the file-group barrier and max / sum, and ONE
+    torch.distributed.run --nproc-per-node 2 bench.py --full --gpus 2 (GC_BENCH_DEVICES=0,0 puts both
+    ranks on device 0; --full for the common-interval leg): one process per rank, the file-group barrier and max / sum, and ONE
     JSON line from rank 0 with n_gpus 2, global_boards 2 x boards, replica_mode processes."""
     import json
     import os
@@ -119,8 +120,8 @@ def test_bench_torchrun_two_ranks_line():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "20", "--warmup", "5", "--settle", "300", "--boards", "8192",
-                          "--perft-roots", "0", "--variant-steps", "0", "--api-steps", "0", "--single-episodes", "0",
+                          "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--settle", "300", "--boards",
+                          "8192", "--perft-roots", "0", "--variant-steps", "0", "--api-steps", "0", "--single-episodes", "0",
                           "--no-cpu-baseline", "--launched-steps", "0"], capture_output=True, text=True, env=env,
                          timeout=240, check=True)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

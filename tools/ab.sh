@@ -25,9 +25,9 @@ fi
 NOLEG="--no-cpu-baseline --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0"
 case $MODE in
   step)  KS=${KS:-"20 1000"}; ARGS="--warmup 5 $NOLEG --perft-roots 0" ;;
-  perft) KS="5"; ARGS="--warmup 5 --settle 0 --no-cpu-baseline --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0" ;;
-  var)   KS="5"; ARGS="--warmup 5 --no-cpu-baseline --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 300 --perft-roots 0 --configs1-roots 0" ;;
-  api|apiv) KS="5"; ARGS="--warmup 5 --settle 0 --no-cpu-baseline --launched-steps 0 --api-steps 200 --single-episodes 0 --variant-steps 0 --perft-roots 0" ;;
+  perft) KS="5"; ARGS="--full --warmup 5 --settle 0 --no-cpu-baseline --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0" ;;
+  var)   KS="5"; ARGS="--full --warmup 5 --no-cpu-baseline --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 300 --perft-roots 0 --configs1-roots 0" ;;
+  api|apiv) KS="5"; ARGS="--full --warmup 5 --settle 0 --no-cpu-baseline --launched-steps 0 --api-steps 200 --single-episodes 0 --variant-steps 0 --perft-roots 0" ;;
   *) echo "unknown MODE $MODE"; exit 2 ;;
 esac
 : > gpurun_out/ab.jsonl

@@ -1,6 +1,6 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-A="python bench.py --no-cpu-baseline --steps 5 --warmup 5 --settle 200 --launched-steps 0 --api-steps 100 --single-episodes 0 --variant-steps 0 --perft-roots 0"
+A="python bench.py --full --no-cpu-baseline --steps 5 --warmup 5 --settle 200 --launched-steps 0 --api-steps 100 --single-episodes 0 --variant-steps 0 --perft-roots 0"
 for nb in 65536; do
   timeout -k 10 120 $A --boards $nb > gpurun_out/api_n$nb.log 2>&1 || exit 3
   python -c "import json;d=json.loads([l for l in open('gpurun_out/api_n$nb.log') if l.startswith('{')][-1]);a=d['api_step'];print($nb, a['value']/1e9, a['roofline']['avg_launch_us'])"

@@ -17,21 +17,21 @@ step() {
 }
 # PMC passes time the bench's own steady-state launches (bench defaults: --settle 1000
 # --warmup 50), 20 of them; one counter group per pass (rocprofv3 does not split passes)
-PMCB="python bench.py --no-cpu-baseline --steps 20 --launched-steps 20 --api-steps 0 --single-episodes 0 --perft-roots 0 --variant-steps 0"
+PMCB="python bench.py --full --no-cpu-baseline --steps 20 --launched-steps 20 --api-steps 0 --single-episodes 0 --perft-roots 0 --variant-steps 0"
 # the headline: the driver's own shape (--steps 20 --warmup 5), the fused launch of 20 steps is
 # the LAST k_env_rollout4 dispatch of the process
 PMCR="python bench.py --no-cpu-baseline --steps 20 --warmup 5 --launched-steps 0 --api-steps 0 --single-episodes 0 --perft-roots 0 --variant-steps 0"
 PMCRL="python bench.py --no-cpu-baseline --steps 1000 --warmup 5 --launched-steps 0 --api-steps 0 --single-episodes 0 --perft-roots 0 --variant-steps 0"  # the K = 1 000 line
 MIXC="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"
 # perft passes: the bench's perft leg (65 536 mid-game FEN roots, perft(5)) without the step legs
-PERFTB="python bench.py --no-cpu-baseline --steps 5 --warmup 5 --settle 0 --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0"
+PERFTB="python bench.py --full --no-cpu-baseline --steps 5 --warmup 5 --settle 0 --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0"
 for s in ${STEPS:-smoke pytest bench prof}; do
   case $s in
     smoke)  step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) step pytest 1100 python -u -m pytest ${PYTEST_ARGS:-tests} -x -v -m gpu --timeout 300 --timeout-method thread ;;  # PYTEST_ARGS: a subset
-    bench)  step bench 600 python bench.py ${BENCH_ARGS:-} ;;
-    prof)   step prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --no-cpu-baseline --oracle-perft-roots 0 ;;  # bench defaults: the same launches bench.py times
-    profs)  step profs 300 rocprofv3 --kernel-trace --stats -d $OUT/profs -o run --output-format csv -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --oracle-perft-roots 0 ;;  # the driver's command
+    bench)  step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
+    prof)   step prof 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python bench.py --full --no-cpu-baseline --oracle-perft-roots 0 ;;  # bench defaults: the same launches bench.py times
+    profs)  step profs 300 rocprofv3 --kernel-trace --stats -d $OUT/profs -o run --output-format csv -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --oracle-perft-roots 0 ;;  # the driver's command with every leg
     pmcf)   step pmcf 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run --output-format csv -- $PMCB ;;
     pmcw)   step pmcw 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc_write -o run --output-format csv -- $PMCB ;;
     pmcv)   step pmcv 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU -d $OUT/pmc_valu -o run --output-format csv -- $PMCB ;;

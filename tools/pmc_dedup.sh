@@ -2,7 +2,7 @@
 # PMC of the perft leg's kernels (the transposition pass -- k_dedup_keys, the radix sort, k_dedup_runs (or k_dedup_bin) -- and the leaf): SQ mix, fetch, write
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 export TMPDIR=/tmp
-P="python bench.py --no-cpu-baseline --steps 5 --warmup 5 --settle 0 --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0"
+P="python bench.py --full --no-cpu-baseline --steps 5 --warmup 5 --settle 0 --launched-steps 0 --api-steps 0 --single-episodes 0 --variant-steps 0 --oracle-perft-roots 0"
 MIXC="SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"
 timeout -s KILL 120 rocprofv3 --pmc $MIXC -d gpurun_out/pd_v -o run --output-format csv -- $P > /dev/null 2>&1 || exit 4
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pd_f -o run --output-format csv -- $P > /dev/null 2>&1 || exit 5
