@@ -84,6 +84,14 @@ GC_HD u64 bop3(u64 a, u64 b, u64 c) {
     return r;
 #endif
 }
+// A bitboard made of bop3's halves, kept one 64-bit value (device: an empty asm on the register
+// pair, no instruction): otherwise a 64-bit shift-add of it is split by halves into two
+GC_HD u64 whole(u64 x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
 GC_HD u64 and_or(u64 a, u64 b, u64 c) { return bop3<0xEA>(a, b, c); }  // (a & b) | c
 GC_HD u64 and3(u64 a, u64 b, u64 c) { return bop3<0x80>(a, b, c); }    // a & b & c
 // squares below s (s < 64): shift-only, so no 64-bit subtract (a VCC carry chain, and on
@@ -252,6 +260,100 @@ GC_HD u64 ray_fill_to(u64 gen, u64 empty, u64 wrap, u64 tm) {
     gen = and_or(pro, sh<4 * SH, LEFT>(gen), gen);
     return and3(sh<SH, LEFT>(gen), wrap, tm);
 }
+// The fill's propagator masks depend on the empty squares only: a caller that fills twice over
+// one occupancy (the enemy map, then the own sets: the quads' phases 1 and 2) builds them once.
+struct RayPro {
+    u64 p0, p1, p2;  // squares a ray may cross in 1, 2 and 4 steps
+};
+template <int SH, bool LEFT>
+GC_HD RayPro ray_pro(u64 empty, u64 wrap) {
+    const u64 p0 = empty & wrap;
+    const u64 p1 = p0 & sh<SH, LEFT>(p0);
+    return RayPro{p0, p1, p1 & sh<2 * SH, LEFT>(p1)};
+}
+template <int SH, bool LEFT>
+GC_HD u64 ray_fill_gen(u64 gen, const RayPro& P) {
+    gen = and_or(P.p0, sh<SH, LEFT>(gen), gen);
+    gen = and_or(P.p1, sh<2 * SH, LEFT>(gen), gen);
+    return and_or(P.p2, sh<4 * SH, LEFT>(gen), gen);
+}
+template <int SH, bool LEFT>
+GC_HD u64 ray_fill_att(u64 gen, const RayPro& P, u64 wrap) {
+    return sh<SH, LEFT>(ray_fill_gen<SH, LEFT>(gen, P)) & wrap;
+}
+template <int SH, bool LEFT>
+GC_HD u64 ray_fill_to(u64 gen, const RayPro& P, u64 wrap, u64 tm) {
+    return and3(sh<SH, LEFT>(ray_fill_gen<SH, LEFT>(gen, P)), wrap, tm);
+}
+
+// ---- rank-direction fills by carry propagation ---------------------------------------------
+// Along a rank the fill of all sliders at once is one borrow: o ^ (o - 2 * gen) sets, for every
+// slider, the squares east of it up to and including the first piece (o - 2s borrows through
+// the empty squares above s and stops at the first occupied one; the regions of two sliders are
+// disjoint, so one subtraction serves them all).  A sentinel on file H ends a borrow on its own
+// rank, and a slider on file H itself has no square to the east.  West is the same on
+// bit-reversed operands (file A becomes file H).  The subtraction is written as additions
+// (-2g = (~g << 1) + 2): v_lshl_add_u64 is one instruction, a 64-bit subtract a VCC carry pair.
+//
+// PRECONDITION: gen is a subset of occ (the generators are pieces).  A generator on an empty
+// square inside another generator's ray would cancel part of that ray's borrow: the result is
+// then NOT the Kogge-Stone one.
+//
+// LEFT = true is east (towards higher bits: ray_fill_*<1, true> with wrap ~FILE_A), LEFT = false
+// is west (ray_fill_*<1, false> with wrap ~FILE_H); same results for gen within occ.
+struct RankOcc {
+    u64 o;   // occ | FILE_H: the east fill's occupancy with its sentinel
+    u64 o2;  // o + 2
+    u64 ow;  // occ | FILE_A: the west fill's, = rbit(its reversed occupancy)
+    u64 r2;  // rbit(ow) + 2
+};
+GC_HD RankOcc rank_occ(u64 occ) {
+    const u64 o = occ | FILE_H, ow = occ | FILE_A;
+    return RankOcc{o, o + 2, ow, rbit(ow) + 2};
+}
+// o - 2 * (gen & ~FILE_H)
+GC_HD u64 rank_borrow_east(u64 gen, const RankOcc& R) { return (whole(bop3<0xCF>(gen, FILE_H, 0ull)) << 1) + R.o2; }
+// the same on the reversed board, reversed back: rbit(rbit(ow) - 2 * (rbit(gen) & ~FILE_H))
+GC_HD u64 rank_borrow_west(u64 gen, const RankOcc& R) {
+    return rbit((whole(bop3<0xCF>(rbit(gen), FILE_H, 0ull)) << 1) + R.r2);
+}
+template <bool LEFT>
+GC_HD u64 rank_fill_att(u64 gen, const RankOcc& R) {
+    return LEFT ? rank_borrow_east(gen, R) ^ R.o : rank_borrow_west(gen, R) ^ R.ow;
+}
+template <bool LEFT>
+GC_HD u64 rank_fill_to(u64 gen, const RankOcc& R, u64 tm) {  // (x ^ o) & tm in one op per half
+    return LEFT ? bop3<0x28>(rank_borrow_east(gen, R), R.o, tm) : bop3<0x28>(rank_borrow_west(gen, R), R.ow, tm);
+}
+template <bool LEFT>
+GC_HD u64 rank_fill_att(u64 gen, u64 occ) { return rank_fill_att<LEFT>(gen, rank_occ(occ)); }
+template <bool LEFT>
+GC_HD u64 rank_fill_to(u64 gen, u64 occ, u64 tm) { return rank_fill_to<LEFT>(gen, rank_occ(occ), tm); }
+// two generator sets over one occupancy (ray_fill_pair's counterpart: the operands are shared)
+template <bool LEFT>
+GC_HD void rank_fill_pair(u64 ge, u64 go, const RankOcc& R, u64& ae, u64& ao) {
+    ae = rank_fill_att<LEFT>(ge, R);
+    ao = rank_fill_att<LEFT>(go, R);
+}
+
+// What the orthogonal fills of one occupancy share: the rank operands and the two vertical
+// directions' propagators.
+struct OrthCarry {
+    RankOcc R;
+    RayPro m8, p8;  // >> 8, << 8
+};
+GC_HD OrthCarry orth_carry(u64 occ) {
+    return OrthCarry{rank_occ(occ), ray_pro<8, false>(~occ, ~0ull), ray_pro<8, true>(~occ, ~0ull)};
+}
+// ... and the diagonal ones: the four directions' propagators
+struct DiagCarry {
+    RayPro m7, m9, p9, p7;  // >> 7 (~FILE_A), >> 9 (~FILE_H), << 9 (~FILE_A), << 7 (~FILE_H)
+};
+GC_HD DiagCarry diag_carry(u64 occ) {
+    const u64 empty = ~occ;
+    return DiagCarry{ray_pro<7, false>(empty, ~FILE_A), ray_pro<9, false>(empty, ~FILE_H),
+                     ray_pro<9, true>(empty, ~FILE_A), ray_pro<7, true>(empty, ~FILE_H)};
+}
 
 // the map in three parts (the quad step kernel computes them on different waves)
 GC_HD u64 side_attacks_leapers(const Pos& s, bool white) {
@@ -260,18 +362,19 @@ GC_HD u64 side_attacks_leapers(const Pos& s, bool white) {
     return (pawn_att_set(s.p & mine, white) & ~(s.k & mine)) | knight_set(s.n & mine) | king_set(s.k & mine);
 }
 // branch-free for any number of sliders (a per-slider loop runs the wave's maximum)
-GC_HD u64 side_attacks_orth(const Pos& s, bool white) {
-    u64 occ = occ_of(s), empty = ~occ;
-    u64 rq = (s.r | s.q) & (white ? s.w : (occ & ~s.w));
-    return ray_fill_att<8, false>(rq, empty, ~0ull) | ray_fill_att<8, true>(rq, empty, ~0ull) |
-           ray_fill_att<1, true>(rq, empty, ~FILE_A) | ray_fill_att<1, false>(rq, empty, ~FILE_H);
+// (c: orth_carry / diag_carry of the position's occupancy)
+GC_HD u64 side_attacks_orth(const Pos& s, bool white, const OrthCarry& c) {
+    u64 rq = (s.r | s.q) & (white ? s.w : (occ_of(s) & ~s.w));
+    return ray_fill_att<8, false>(rq, c.m8, ~0ull) | ray_fill_att<8, true>(rq, c.p8, ~0ull) |
+           rank_fill_att<true>(rq, c.R) | rank_fill_att<false>(rq, c.R);
 }
-GC_HD u64 side_attacks_diag(const Pos& s, bool white) {
-    u64 occ = occ_of(s), empty = ~occ;
-    u64 bq = (s.b | s.q) & (white ? s.w : (occ & ~s.w));
-    return ray_fill_att<7, false>(bq, empty, ~FILE_A) | ray_fill_att<9, false>(bq, empty, ~FILE_H) |
-           ray_fill_att<9, true>(bq, empty, ~FILE_A) | ray_fill_att<7, true>(bq, empty, ~FILE_H);
+GC_HD u64 side_attacks_orth(const Pos& s, bool white) { return side_attacks_orth(s, white, orth_carry(occ_of(s))); }
+GC_HD u64 side_attacks_diag(const Pos& s, bool white, const DiagCarry& c) {
+    u64 bq = (s.b | s.q) & (white ? s.w : (occ_of(s) & ~s.w));
+    return ray_fill_att<7, false>(bq, c.m7, ~FILE_A) | ray_fill_att<9, false>(bq, c.m9, ~FILE_H) |
+           ray_fill_att<9, true>(bq, c.p9, ~FILE_A) | ray_fill_att<7, true>(bq, c.p7, ~FILE_H);
 }
+GC_HD u64 side_attacks_diag(const Pos& s, bool white) { return side_attacks_diag(s, white, diag_carry(occ_of(s))); }
 GC_HD u64 side_attacks(const Pos& s, bool white) {
     return side_attacks_leapers(s, white) | side_attacks_orth(s, white) | side_attacks_diag(s, white);
 }
@@ -1004,26 +1107,29 @@ GC_HD void sw_knights(const Pos& s, const Gen& g, u64* t, u64 xm = ~0ull) {
     t[SW_N + 6] = (l2 >> 8) & tm;   // - 10
     t[SW_N + 7] = (r2 >> 8) & tm;   // - 6
 }
-GC_HD void sw_orth(const Pos& s, const Gen& g, u64* t, u64 xm = ~0ull) {
+// (c: orth_carry / diag_carry of g.occ, shared with the enemy map's fills where both are made)
+GC_HD void sw_orth(const Pos& s, const Gen& g, const OrthCarry& c, u64* t, u64 xm = ~0ull) {
     const int kq = sw_ksq(g);
     const u64 S = (s.r | s.q) & g.own, fr = S & ~g.pinned, pp = S & g.pinned;
-    const u64 empty = ~g.occ, tm = ~g.own & g.checkmask & xm;
+    const u64 tm = ~g.own & g.checkmask & xm;
     const u64 gf = fr | (pp & file_mask(kq)), gr = fr | (pp & row_mask(kq));
-    t[SW_ORTH + 0] = ray_fill_to<8, false>(gf, empty, ~0ull, tm);
-    t[SW_ORTH + 1] = ray_fill_to<8, true>(gf, empty, ~0ull, tm);
-    t[SW_ORTH + 2] = ray_fill_to<1, true>(gr, empty, ~FILE_A, tm);
-    t[SW_ORTH + 3] = ray_fill_to<1, false>(gr, empty, ~FILE_H, tm);
+    t[SW_ORTH + 0] = ray_fill_to<8, false>(gf, c.m8, ~0ull, tm);
+    t[SW_ORTH + 1] = ray_fill_to<8, true>(gf, c.p8, ~0ull, tm);
+    t[SW_ORTH + 2] = rank_fill_to<true>(gr, c.R, tm);
+    t[SW_ORTH + 3] = rank_fill_to<false>(gr, c.R, tm);
 }
-GC_HD void sw_diag(const Pos& s, const Gen& g, u64* t, u64 xm = ~0ull) {
+GC_HD void sw_orth(const Pos& s, const Gen& g, u64* t, u64 xm = ~0ull) { sw_orth(s, g, orth_carry(g.occ), t, xm); }
+GC_HD void sw_diag(const Pos& s, const Gen& g, const DiagCarry& c, u64* t, u64 xm = ~0ull) {
     const int kq = sw_ksq(g);
     const u64 S = (s.b | s.q) & g.own, fr = S & ~g.pinned, pp = S & g.pinned;
-    const u64 empty = ~g.occ, tm = ~g.own & g.checkmask & xm;
+    const u64 tm = ~g.own & g.checkmask & xm;
     const u64 gd = fr | (pp & diag_mask(kq)), ga = fr | (pp & anti_mask(kq));
-    t[SW_DIAG + 0] = ray_fill_to<7, false>(ga, empty, ~FILE_A, tm);
-    t[SW_DIAG + 1] = ray_fill_to<9, false>(gd, empty, ~FILE_H, tm);
-    t[SW_DIAG + 2] = ray_fill_to<9, true>(gd, empty, ~FILE_A, tm);
-    t[SW_DIAG + 3] = ray_fill_to<7, true>(ga, empty, ~FILE_H, tm);
+    t[SW_DIAG + 0] = ray_fill_to<7, false>(ga, c.m7, ~FILE_A, tm);
+    t[SW_DIAG + 1] = ray_fill_to<9, false>(gd, c.m9, ~FILE_H, tm);
+    t[SW_DIAG + 2] = ray_fill_to<9, true>(gd, c.p9, ~FILE_A, tm);
+    t[SW_DIAG + 3] = ray_fill_to<7, true>(ga, c.p7, ~FILE_H, tm);
 }
+GC_HD void sw_diag(const Pos& s, const Gen& g, u64* t, u64 xm = ~0ull) { sw_diag(s, g, diag_carry(g.occ), t, xm); }
 // the diagonal sets SW_DIAG + lo .. SW_DIAG + hi - 1 only (the paired driver splits them
 // between its two waves)
 template <int lo, int hi>
@@ -1115,9 +1221,10 @@ GC_HD int count_nonsliders(const Pos& s, const Gen& g) { return count_nonsliders
 GC_HD int count_moves(const Pos& s, const Gen& g) {
     const u64 tm = ~g.own & g.checkmask, empty = ~g.occ;
     const SliderGens G = slider_gens(s, g);
+    const RankOcc R = rank_occ(g.occ);
     return count_nonsliders(s, g) +
            ray_count<8, false>(G.f, empty, ~0ull, tm) + ray_count<8, true>(G.f, empty, ~0ull, tm) +
-           ray_count<1, true>(G.r, empty, ~FILE_A, tm) + ray_count<1, false>(G.r, empty, ~FILE_H, tm) +
+           popc(rank_fill_to<true>(G.r, R, tm)) + popc(rank_fill_to<false>(G.r, R, tm)) +
            ray_count<7, false>(G.a, empty, ~FILE_A, tm) + ray_count<9, false>(G.d, empty, ~FILE_H, tm) +
            ray_count<9, true>(G.d, empty, ~FILE_A, tm) + ray_count<7, true>(G.a, empty, ~FILE_H, tm);
 }
@@ -1153,6 +1260,7 @@ GC_HD int count_position_kl(const Pos& s, const KingLines& kh, const u64* ntab =
     const u64 empty = ~g.occ, tm = ~g.own & g.checkmask;
     const u64 eRQ = (s.r | s.q) & g.opp, eBQ = (s.b | s.q) & g.opp;
     const SliderGens G = slider_gens_kl(s, g, kl);
+    const RankOcc R = rank_occ(g.occ);
     u64 att = 0, ae, ao;
     int n = 0;
 #define GC_PAIR(SH, LEFT, GE, GO, WRAP)                  \
@@ -1161,8 +1269,12 @@ GC_HD int count_position_kl(const Pos& s, const KingLines& kh, const u64* ntab =
     n += popc(ao & tm);
     GC_PAIR(8, false, eRQ, G.f, ~0ull)
     GC_PAIR(8, true, eRQ, G.f, ~0ull)
-    GC_PAIR(1, true, eRQ, G.r, ~FILE_A)
-    GC_PAIR(1, false, eRQ, G.r, ~FILE_H)
+    rank_fill_pair<true>(eRQ, G.r, R, ae, ao);
+    att |= ae;
+    n += popc(ao & tm);
+    rank_fill_pair<false>(eRQ, G.r, R, ae, ao);
+    att |= ae;
+    n += popc(ao & tm);
     GC_PAIR(7, false, eBQ, G.a, ~FILE_A)
     GC_PAIR(9, false, eBQ, G.d, ~FILE_H)
     GC_PAIR(9, true, eBQ, G.d, ~FILE_A)

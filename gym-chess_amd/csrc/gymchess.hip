@@ -2225,6 +2225,11 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     // ---- phase 1
     Gen g;
     bool my_chk = false;
+    // Q2 / Q3 fill twice over the post-move board's occupancy, the enemy's sliders here and the own
+    // ones in phase 2: the rank operands and the propagator masks are built once and held across
+    // the barrier (10 and 12 u64; these two roles carry no state)
+    OrthCarry oc{};
+    DiagCarry dc{};
     if (R != 0) {
         ns.k = L.ns[0][l]; ns.q = L.ns[1][l]; ns.r = L.ns[2][l]; ns.b = L.ns[3][l];
         ns.n = L.ns[4][l]; ns.p = L.ns[5][l]; ns.w = L.ns[6][l];
@@ -2257,9 +2262,11 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         oq.probe = !oq.valid || ((L.occ[(nk & (HTAB - 1)) >> 6][l] >> (nk & 63)) & 1) != 0;
         }
     } else if (R == 2) {
-        L.enemy[1][l] = g.ks >= 0 ? side_attacks_leapers(ns, !g.white) | side_attacks_orth(ns, !g.white) : 0ull;
+        oc = orth_carry(g.occ);
+        L.enemy[1][l] = g.ks >= 0 ? side_attacks_leapers(ns, !g.white) | side_attacks_orth(ns, !g.white, oc) : 0ull;
     } else {
-        L.enemy[2][l] = g.ks >= 0 ? side_attacks_diag(ns, !g.white) : 0ull;
+        dc = diag_carry(g.occ);
+        L.enemy[2][l] = g.ks >= 0 ? side_attacks_diag(ns, !g.white, dc) : 0ull;
     }
     PST(2);
     pair_barrier();
@@ -2318,7 +2325,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         L.ra[l] = ra;
     } else if (R == 2) {  // unconditional: ignored unless generation is due
         u64 T[SW_SETS];
-        sw_orth(ns, g, T);
+        sw_orth(ns, g, oc, T);
         Q.put_all<SW_ORTH, SW_DIAG>(T + SW_ORTH);
         sw_kings(ns, g, T);
         Q.put_all<SW_K, SW_SETS>(T + SW_K);
@@ -2327,7 +2334,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         for (int k = 0; k < 4; k++) L.cwx[0][k][l] = Q.cw[k];
     } else {
         u64 T[SW_SETS];
-        sw_diag(ns, g, T);
+        sw_diag(ns, g, dc, T);
         Q.put_all<SW_DIAG, SW_K>(T + SW_DIAG);
         L.part[3][l] = (u32)Q.part;
 #pragma unroll
@@ -3832,6 +3839,8 @@ __device__ __forceinline__ void apiqv_run(uint8_t* __restrict__ slab, uint64_t s
     }
     Gen g;
     gen_base(ns, g);
+    OrthCarry orc{};  // Q2 / Q3: the fills' shared operands, phase 1 -> 2 (as quad_ply)
+    DiagCarry dgc{};
     if (RR == 0) {
         gen_pins(ns, g);
         L.pin3[0][l] = g.checkmask;
@@ -3841,9 +3850,11 @@ __device__ __forceinline__ void apiqv_run(uint8_t* __restrict__ slab, uint64_t s
     } else if (RR == 1) {
         L.f1[l] = (mv && mover_checked(s, ns, white, a)) ? 1u : 0u;
     } else if (RR == 2) {
-        L.enemy[1][l] = g.ks >= 0 ? side_attacks_leapers(ns, !g.white) | side_attacks_orth(ns, !g.white) : 0ull;
+        orc = orth_carry(g.occ);
+        L.enemy[1][l] = g.ks >= 0 ? side_attacks_leapers(ns, !g.white) | side_attacks_orth(ns, !g.white, orc) : 0ull;
     } else {
-        L.enemy[2][l] = g.ks >= 0 ? side_attacks_diag(ns, !g.white) : 0ull;
+        dgc = diag_carry(g.occ);
+        L.enemy[2][l] = g.ks >= 0 ? side_attacks_diag(ns, !g.white, dgc) : 0ull;
     }
     PST(1);
     pair_barrier();
@@ -3890,7 +3901,7 @@ __device__ __forceinline__ void apiqv_run(uint8_t* __restrict__ slab, uint64_t s
         L.ra[1][l] = ra1;
     } else if (RR == 2) {  // unconditional: ignored unless the opponent's moves are due
         u64 T[SW_SETS];
-        sw_orth(ns, g, T);
+        sw_orth(ns, g, orc, T);
         Q.put_all<SW_ORTH, SW_DIAG>(T + SW_ORTH);
         sw_kings(ns, g, T);
         Q.put_all<SW_K, SW_SETS>(T + SW_K);
@@ -3899,7 +3910,7 @@ __device__ __forceinline__ void apiqv_run(uint8_t* __restrict__ slab, uint64_t s
         for (int k = 0; k < 4; k++) L.sc.cwx[0][k][l] = Q.cw[k];
     } else {
         u64 T[SW_SETS];
-        sw_diag(ns, g, T);
+        sw_diag(ns, g, dgc, T);
         Q.put_all<SW_DIAG, SW_K>(T + SW_DIAG);
         L.part[3][l] = (u32)Q.part;
 #pragma unroll
