@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,6 +71,7 @@ __device__ __forceinline__ void gc_pst_mark(int k) {
 #include "gc_env.h"
 #include "gc_perft.h"
 #include "gc_fide.h"
+#include "gc_policy.h"
 #include "../../include/gymchess.h"
 
 using namespace gc;
@@ -6306,6 +6308,44 @@ extern "C" int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t*
                                   uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
                                   uint16_t* d_pick, int flags) {
     return gc_env_step_device2(e, d_actions, d_reward, d_done, d_reason, d_mask, d_obs, d_count, d_pick, flags, 0);
+}
+
+// Policy head on the device (gc_policy.h): per board an action sampled from softmax(logits / T)
+// over the legal mask that gc_env_step_device2 wrote (or the greedy one), its log-prob and the
+// entropy.  Reads only the mask and the logits at legal actions: either rule set, either
+// opponent mode.  Asynchronous on the env's stream, so a following gc_env_step_device2 that
+// takes d_action as its actions is ordered after it.
+extern "C" int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
+                                    const uint64_t* d_mask, int64_t mask_stride, float temperature,
+                                    uint64_t seed, uint32_t draw, int flags,
+                                    uint16_t* d_action, float* d_logprob, float* d_entropy) {
+    if (!e || !d_logits || !d_mask || !d_action) return fail("null argument");
+    if (dtype < 0 || dtype > 2) return fail("dtype: 0 float32, 1 float16, 2 bfloat16");
+    if (row_stride < 4100) return fail("row stride below the 4100 move actions");
+    if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0");
+    if (flags & ~1) return fail("flags: bit 0 = greedy");
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    PolicyArgs a;
+    a.logits = d_logits;
+    a.row_stride = (size_t)row_stride;
+    a.mask = d_mask;
+    a.mask_stride = mask_stride ? (size_t)mask_stride : (size_t)e->n;
+    a.temperature = temperature;
+    a.seed = seed;
+    a.draw = draw;
+    a.greedy = flags & 1;
+    a.action = d_action;
+    a.logprob = d_logprob;
+    a.entropy = d_entropy;
+    a.n = e->n;
+    const dim3 grid((e->n + POL_TILE - 1) / POL_TILE), block(64 * POL_WAVES);
+    if (dtype == 0) k_sample_policy<0><<<grid, block, 0, e->stream>>>(a);
+    else if (dtype == 1) k_sample_policy<1><<<grid, block, 0, e->stream>>>(a);
+    else k_sample_policy<2><<<grid, block, 0, e->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int gc_env_get_stream(gc_env* e, void** stream) {

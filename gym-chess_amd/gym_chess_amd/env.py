@@ -277,11 +277,13 @@ class BatchedChessEnv:
         return int(self._L.gc_env_device_bytes(self._h))
 
     # ------------------------------------------------------------------ device-buffer step
-    def device_io(self, mask=True, obs=True, count=True, pick=True, select=True, mask_stride=None):
+    def device_io(self, mask=True, obs=True, count=True, pick=True, select=True, mask_stride=None, policy=False):
         """Device buffers for step_device (gc_device_alloc on this env's device); with pick and
         select, the pick buffer starts as the random policy's actions for the current states.
-        mask_stride: the mask's row stride in words (>= N; None = DeviceIO.default_mask_stride)."""
-        return DeviceIO(self, mask=mask, obs=obs, count=count, pick=pick, select=select, mask_stride=mask_stride)
+        mask_stride: the mask's row stride in words (>= N; None = DeviceIO.default_mask_stride).
+        policy: also logprob and entropy (float32[N]), sample_policy's optional outputs."""
+        return DeviceIO(self, mask=mask, obs=obs, count=count, pick=pick, select=select, mask_stride=mask_stride,
+                        policy=policy)
 
     def step_device(self, io, actions=None, autoreset=False):
         """step() on device buffers (gc_env_step_device), asynchronous on the env's stream.
@@ -294,6 +296,33 @@ class BatchedChessEnv:
         _lib.check(self._L.gc_env_step_device2(self._h, a, p["reward"], p["done"], p["reason"], p.get("mask"),
                                                p.get("obs"), p.get("count"), p.get("pick"), int(bool(autoreset)),
                                                io.mask_stride))
+
+    POLICY_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+
+    def sample_policy(self, io, logits, dtype="float32", row_stride=4100, temperature=1.0, seed=None, draw=0,
+                      greedy=False, action=None):
+        """Actions for the positions io.mask describes, from a network's logits on the device
+        (gc_env_sample_policy): per board one sample of softmax(logits / temperature) over its
+        legal actions (greedy: the argmax), asynchronous on the env's stream.
+        logits: a device pointer (int, e.g. a torch tensor's data_ptr()) to [N][row_stride]
+        elements of `dtype` ("float32" / "float16" / "bfloat16"), element a of a row = the logit
+        of action a (0..4099).  seed: None = the env's; draw: a counter the caller advances per
+        call (same seed and draw = same uniforms).  action: a device pointer to uint16[N], None =
+        io's pick buffer, which step_device(io) then plays.  With device_io(policy=True) the
+        log-probs and entropies land in io's logprob / entropy buffers."""
+        if dtype not in self.POLICY_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
+        p = io.ptr
+        if not p.get("mask"):
+            raise ValueError("no legal mask: allocate io with mask=True")
+        a = p.get("pick") if action is None else int(action)
+        if not a:
+            raise ValueError("no action buffer: pass a device pointer or allocate io with pick=True")
+        _lib.check(self._L.gc_env_sample_policy(self._h, int(logits), self.POLICY_DTYPES[dtype], int(row_stride),
+                                                p["mask"], io.mask_stride, float(temperature),
+                                                ctypes.c_uint64(self.seed if seed is None else int(seed)),
+                                                int(draw) & 0xFFFFFFFF, int(bool(greedy)), a, p.get("logprob"),
+                                                p.get("entropy")))
 
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""
@@ -370,11 +399,13 @@ class DeviceIO:
     """Device buffers of one env's step_device outputs: reward i32, done u8, reason u8 and
     optionally mask u64[65][stride] (word-major: word f of board i at f * stride + i, stride >= N),
     obs i8[N][64], count i32, pick u16 (the random policy's next action, which step_device uses
-    as the actions when given none).  fetch() copies them to host arrays; upload_actions() fills
+    as the actions when given none), and with policy=True logprob f32 and entropy f32
+    (sample_policy's outputs).  fetch() copies them to host arrays; upload_actions() fills
     the pick buffer from the host."""
 
     _SPEC = {"reward": (np.int32, ()), "done": (np.uint8, ()), "reason": (np.uint8, ()),
-             "mask": (np.uint64, (65,)), "obs": (np.int8, (64,)), "count": (np.int32, ()), "pick": (np.uint16, ())}
+             "mask": (np.uint64, (65,)), "obs": (np.int8, (64,)), "count": (np.int32, ()), "pick": (np.uint16, ()),
+             "logprob": (np.float32, ()), "entropy": (np.float32, ())}
 
     @staticmethod
     def default_mask_stride(n):
@@ -388,13 +419,15 @@ class DeviceIO:
 
     MASK_PAD = 512
 
-    def __init__(self, env, mask=True, obs=True, count=True, pick=True, select=True, mask_stride=None):
+    def __init__(self, env, mask=True, obs=True, count=True, pick=True, select=True, mask_stride=None,
+                 policy=False):
         self.env = env
         n = env.num_boards
         self.mask_stride = int(self.default_mask_stride(n) if mask_stride is None else mask_stride)
         if self.mask_stride < n:
             raise ValueError(f"mask_stride {self.mask_stride} < num_boards {n}")
-        want = {"reward": True, "done": True, "reason": True, "mask": mask, "obs": obs, "count": count, "pick": pick}
+        want = {"reward": True, "done": True, "reason": True, "mask": mask, "obs": obs, "count": count, "pick": pick,
+                "logprob": policy, "entropy": policy}
         self.ptr = {}
         for k, on in want.items():
             if not on:

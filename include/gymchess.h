@@ -172,6 +172,27 @@ int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, 
 int gc_env_step_device2(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, uint8_t* d_done,
                         uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
                         uint16_t* d_pick, int flags, int64_t mask_stride);
+/* Policy head for a network on the GPU: per board an action drawn from softmax(logits / T) over
+ * the legal actions of a mask gc_env_step_device2 wrote, without unpacking the mask or reading
+ * the other ~4070 logits of the row.  d_logits: row i at element i * row_stride (>= 4100),
+ * element a = the logit of action a (from*64+to, 4096..4099 the castles); dtype 0 float32,
+ * 1 float16, 2 bfloat16.  d_mask / mask_stride: as gc_env_step_device2 (0 = n).  The legal
+ * actions a_1 < ... < a_m are the mask's set bits in action-id order (d_pick's order), x_k =
+ * logit[a_k] / temperature in fp32, p = softmax(x).  d_action[i]: sampling -- the first k with
+ * u < p_1 + ... + p_k, u = (philox_x0(seed, i, draw) >> 8) * 2^-24 (the caller advances draw
+ * per call), else the last k with p_k > 0; flags bit 0 (greedy) -- the largest x, ties to the
+ * lowest action id.  d_logprob[i] (NULL = skip) = x_j - logsumexp(x) of the chosen j (at the
+ * given temperature in greedy mode too), d_entropy[i] (NULL = skip) = -sum p_k log p_k.  No
+ * legal action: 0xFFFF, 0, 0.  A NaN legal logit, or every legal logit -inf: 0xFFFF, NaN, NaN.
+ * A legal -inf has probability 0 and is never chosen; illegal actions' logits are never used,
+ * whatever they hold.  Any mask works (0..4100 bits), any n.  Asynchronous on the env's stream:
+ * a following gc_env_step_device2 may take d_action as its d_actions.  Fails on a NULL logits /
+ * mask / action, an unknown dtype, row_stride < 4100, 0 < mask_stride < n, a temperature that
+ * is not finite or <= 0.  Either rule set, either opponent mode (only the mask is read). */
+int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
+                         const uint64_t* d_mask, int64_t mask_stride, float temperature,
+                         uint64_t seed, uint32_t draw, int flags,
+                         uint16_t* d_action, float* d_logprob, float* d_entropy);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
