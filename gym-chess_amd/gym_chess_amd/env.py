@@ -67,12 +67,14 @@ class BatchedChessEnv:
             pass
 
     # ------------------------------------------------------------------ gym surface
-    def reset(self, mask=None):
+    def reset(self, mask=None, states=True):
+        """reset every board, or those with mask[i] != 0; states=False skips building the N state
+        dicts of the return value (a driver that resets a few boards of a wide env every step)"""
         m = None
         if mask is not None:
             m = np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.num_boards)
         _lib.check(self._L.gc_env_reset(self._h, _lib.ptr(m) if m is not None else None))
-        return self.state()
+        return self.state() if states else None
 
     def step(self, actions):
         a = np.ascontiguousarray(actions, dtype=np.int64).reshape(self.num_boards)

@@ -831,6 +831,114 @@ void oracle_rollout_digests(const int8_t *init, uint64_t seed, uint32_t b_begin,
     free(th);
 }
 
+/* Full-trajectory digests of the device API step (gc_env_step_device, auto-reset on): one board's
+ * loop of external actions -- mostly the previous call's pick, some arbitrary ones, some near
+ * misses of the pick -- with every step's outputs folded into a 64-bit digest, the legal-action
+ * mask and the observation every mask_every steps, a snapshot of the digest every snap_every
+ * steps, and the final state.  A board left without a legal move (and not done) is reset as the
+ * host reset does (one policy draw in move-set order), so no step is spent on it.
+ * tests/test_api_digest.py restates the loop in Python over the env handle API below and runs
+ * it on the device.
+ * stats: [0..15] steps by reason code, [16] stuck resets, [17] arbitrary actions fed, [18] of
+ * them accepted (reason != 6), [19] near misses fed, [20] accepted, [21] steps fed to a board
+ * with no legal move, [22] the longest legal list, [23] episode ends, [24] accepted near misses
+ * that differ from the pick. */
+#define API_STATS 32
+#define API_ACTION_STREAM 0x5EEDAC7105ull
+static uint64_t api_board(const int8_t *init, uint64_t seed, uint32_t board, int steps, int opp, int agent_black,
+                          int mask_every, int snap_every, uint64_t *snap, size_t snap_stride, uint64_t *stats) {
+    OEnv e;
+    memset(&e, 0, sizeof(e));
+    memcpy(e.init, init, 64);
+    e.opp = opp; e.agent_black = agent_black; e.seed = seed; e.board = board; e.draw = 0;
+    e.set_order = 1;
+    o_env_reset(&e);
+    int a = e.nmoves ? env_policy_pick(&e) : 0xFFFF;  /* the env's creation-time pick */
+    uint64_t d = 0, w;
+    for (int p = 0; p < steps; p++) {
+        uint32_t s = oracle_policy_index(seed ^ API_ACTION_STREAM, board, (uint32_t)p, 16);
+        uint32_t r = oracle_policy_index(seed ^ API_ACTION_STREAM, board, (uint32_t)p + 0x80000000u, 4101);
+        int act = a, cls = 0;
+        if (s == 0) { act = (int)r; cls = 1; }
+        else if (s == 1) { act = a < 4096 ? ((a & 0xFC0) | (int)(r & 63)) : 4096 + (int)(r & 3); cls = 2; }
+        if (e.nmoves == 0) stats[21]++;
+        int rw = 0, dn = 0, why = 0;
+        if (o_env_step(&e, act, &rw, &dn, &why) == 1) { dn = 1; why = 5; }
+        stats[why & 15]++;
+        if (cls) {
+            stats[15 + 2 * cls]++;
+            if (why != 6) stats[16 + 2 * cls]++;
+            if (cls == 2 && why != 6 && act != a) stats[24]++;
+        }
+        if (dn) { stats[23]++; o_env_reset(&e); }
+        int count = e.nmoves, pick = 0xFFFF;
+        if ((uint64_t)count > stats[22]) stats[22] = (uint64_t)count;
+        if (count) pick = kth_in_action_order(e.moves, count, (int)oracle_policy_index(seed, board, e.draw++, (uint32_t)count));
+        d = digest_fold(d, oracle_trace_word(act, rw, dn, why));
+        d = digest_fold(d, (uint64_t)pick | ((uint64_t)count << 16));
+        if ((p + 1) % mask_every == 0) {
+            uint64_t m[65];
+            memset(m, 0, sizeof(m));
+            for (int k = 0; k < count; k++) m[e.moves[k] >> 6] |= 1ull << (e.moves[k] & 63);
+            for (int f = 0; f < 65; f++) d = digest_fold(d, m[f]);
+            for (int q = 0; q < 8; q++) { memcpy(&w, e.st.b + 8 * q, 8); d = digest_fold(d, w); }
+        }
+        if ((p + 1) % snap_every == 0) snap[(size_t)((p + 1) / snap_every - 1) * snap_stride] = d;
+        if (count == 0) {
+            stats[16]++;
+            o_env_reset(&e);
+            a = e.nmoves ? env_policy_pick(&e) : 0xFFFF;
+        } else a = pick;
+    }
+    uint8_t fm[8] = {e.st.player == WHITE, e.st.wkc, e.st.wqc, e.st.bkc, e.st.bqc, e.st.wchk, e.st.bchk, (uint8_t)e.move_count};
+    for (int q = 0; q < 8; q++) { memcpy(&w, e.st.b + 8 * q, 8); d = digest_fold(d, w); }
+    memcpy(&w, fm, 8);
+    d = digest_fold(d, w);
+    free(e.saved);
+    free(e.cnt);
+    return d;
+}
+typedef struct {
+    const int8_t *init; uint64_t seed; int steps, opp, agent_black, mask_every, snap_every; uint32_t b_begin, n;
+    atomic_uint *next; uint64_t *snap, *final; uint64_t stats[API_STATS];
+} AJob;
+static void *ajob_run(void *arg) {
+    AJob *j = (AJob *)arg;
+    for (;;) {
+        uint32_t k = atomic_fetch_add(j->next, 1u);
+        if (k >= j->n) break;
+        j->final[k] = api_board(j->init, j->seed, j->b_begin + k, j->steps, j->opp, j->agent_black, j->mask_every,
+                                j->snap_every, j->snap + k, j->n, j->stats);
+    }
+    return NULL;
+}
+/* snap: [steps / snap_every][n_boards], final: [n_boards], stats: [API_STATS] summed over the boards */
+void oracle_api_digests(const int8_t *init, uint64_t seed, uint32_t b_begin, uint32_t n_boards, int steps, int opp,
+                        int agent_white, int mask_every, int snap_every, int threads, uint64_t *snap, uint64_t *final,
+                        uint64_t *stats) {
+    if (threads < 1) threads = 1;
+    atomic_uint next;
+    atomic_init(&next, 0u);
+    AJob *jobs = (AJob *)calloc((size_t)threads, sizeof(AJob));
+    pthread_t *th = (pthread_t *)calloc((size_t)threads, sizeof(pthread_t));
+    for (int t = 0; t < threads; t++) {
+        jobs[t].init = init; jobs[t].seed = seed; jobs[t].steps = steps; jobs[t].opp = opp; jobs[t].agent_black = !agent_white;
+        jobs[t].mask_every = mask_every; jobs[t].snap_every = snap_every; jobs[t].b_begin = b_begin; jobs[t].n = n_boards;
+        jobs[t].next = &next; jobs[t].snap = snap; jobs[t].final = final;
+        pthread_create(&th[t], NULL, ajob_run, &jobs[t]);
+    }
+    memset(stats, 0, API_STATS * sizeof(uint64_t));
+    for (int t = 0; t < threads; t++) {
+        pthread_join(th[t], NULL);
+        for (int i = 0; i < API_STATS; i++) {
+            if (i == 22) { if (jobs[t].stats[i] > stats[i]) stats[i] = jobs[t].stats[i]; }
+            else stats[i] += jobs[t].stats[i];
+        }
+    }
+    free(jobs);
+    free(th);
+}
+
 /* Trajectory with an opponent mode (0 none, 1 random) and agent colour; order -1 or 1: the
  * policy's move-set order, 0: action-id order (the API step's `pick` output). */
 void oracle_rollout_trace3(const int8_t *init, uint64_t seed, uint32_t board, int plies, int opp, int agent_white,

@@ -102,6 +102,8 @@ def lib():
         L.oracle_rollout_digests.restype = None
         L.oracle_trace_word.argtypes = [i32, i32, i32, i32]
         L.oracle_trace_word.restype = u64
+        L.oracle_api_digests.argtypes = [P, u64, u32, u32, i32, i32, i32, i32, i32, i32, P, P, P]
+        L.oracle_api_digests.restype = None
         _lib = L
     return _lib
 
@@ -240,6 +242,30 @@ def rollout_digests(seed, n_boards, plies, opponent=0, agent_white=True, threads
     lib().oracle_rollout_digests(_p(init), seed, b_begin, n_boards, plies, int(opponent), int(bool(agent_white)),
                                  threads, _p(out))
     return out
+
+
+API_ACTION_STREAM = 0x5EEDAC7105  # seed ^ this: the Philox key of api_digests' action schedule
+API_STAT_NAMES = ("stuck_resets", "arbitrary", "arbitrary_accepted", "near_miss", "near_miss_accepted",
+                  "stuck_steps", "max_count", "episode_ends", "near_miss_changed_accepted")
+
+
+def api_digests(seed, n_boards, steps, opponent=0, agent_white=True, threads=1, init=DEFAULT_BOARD, b_begin=0,
+                mask_every=100, snap_every=500):
+    """Per board b_begin + k, digests of the device API step's loop (gc_oracle.c api_board: the
+    previous pick, arbitrary actions and near misses fed to the auto-reset step; a board without a
+    legal move reset as the host reset does): every step's trace word and pick | count << 16
+    folded d = (d ^ w) * DIGEST_PRIME, the 65 mask words and the observation every mask_every
+    steps, then the final board and meta.  -> (snap uint64[steps // snap_every][n], final
+    uint64[n], stats dict: "reasons" int64[16] steps by reason code + API_STAT_NAMES)."""
+    init = np.ascontiguousarray(init, dtype=np.int8).reshape(64)
+    snap = np.zeros((steps // snap_every, n_boards), dtype=np.uint64)
+    final = np.zeros(n_boards, dtype=np.uint64)
+    st = np.zeros(32, dtype=np.uint64)
+    lib().oracle_api_digests(_p(init), seed, b_begin, n_boards, steps, int(opponent), int(bool(agent_white)),
+                             int(mask_every), int(snap_every), threads, _p(snap), _p(final), _p(st))
+    stats = {"reasons": st[:16].astype(np.int64)}
+    stats.update({k: int(v) for k, v in zip(API_STAT_NAMES, st[16:])})
+    return snap, final, stats
 
 
 class OracleEnv:

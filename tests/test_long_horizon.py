@@ -39,11 +39,14 @@ def test_soak_full_size_20000_plies(oracle, seed, opp, color):
 @pytest.mark.parametrize("seed,color", [(778001, "WHITE"), (778002, "BLACK")])
 def test_api_opponent_full_size(oracle, seed, color):
     """65 536 boards x 3 000 API steps against the random opponent, 192 sampled boards checked
-    step by step (reward, done, reason, the next pick) and their states every 500 steps."""
+    step by step (reward, done, reason, the next pick) and their states every 500 steps.  A board
+    left without a legal move is reset (the host reset), so every checked step is a real one:
+    no step of any of the 65 536 boards is fed to a position without a legal move."""
     import numpy as np
     import soak
 
     idx = np.array(sorted(set(range(0, N, 1021)) | set(range(64)) | set(range(N - 64, N))), dtype=np.int64)
-    bad, steps, spill, secs = soak.api_opp_case(seed, color, 3000, N, idx)
+    bad, steps, spill, secs, stuck_steps = soak.api_opp_case(seed, color, 3000, N, idx)
     print(f"api opponent {color} seed {seed}: {steps} board steps equal, spill {spill}, {secs} s")
     assert not bad and steps == 3000 * len(idx), bad[:8]
+    assert stuck_steps == 0

@@ -42,7 +42,13 @@ def main():
                     help="instead: rules='fide' fused rollouts vs the host build of gc_fide.h (tests/core_host)")
     ap.add_argument("--random-inits", type=int, default=0,
                     help="instead: K random (also weird) initial boards, 4 096 boards each (tests/conftest.py)")
+    ap.add_argument("--api-digest", choices=["none", "random_white", "random_black"],
+                    help="instead: replay --board of this tests/test_api_digest.py case step by step (the API "
+                         "step fed picks, arbitrary actions and near misses) against the oracle env, every field")
+    ap.add_argument("--board", type=int, default=0, help="the board id for --api-digest")
     a = ap.parse_args()
+    if a.api_digest:
+        return api_digest_replay(a)
     if a.api:
         return api_soak(a)
     if a.api_opp:
@@ -184,7 +190,11 @@ def api_soak(a):
 def api_opp_case(seed, color, plies, n, idx):
     """The random opponent's device API step (auto-reset, actions = the previous picks) against
     the oracle env on the boards idx: every step's reward / done / reason and pick, the states
-    every 500 plies.  -> (mismatches, board steps checked, spill info, seconds)"""
+    every 500 plies.  A board left without a legal move and not done (pick 0xFFFF) is reset by
+    the host reset, whose policy pick is its next action (the oracle: reset and one pick), so
+    every checked step is a real step.
+    -> (mismatches, board steps checked, spill info, seconds, steps fed to a board with no
+    legal move)"""
     import oracle as O
     from gym_chess_amd.env import BatchedChessEnv
 
@@ -195,8 +205,9 @@ def api_opp_case(seed, color, plies, n, idx):
     for o in ors.values():
         o.pick()
     prev = io.fetch("pick")["pick"].astype(np.int64)
-    bad, steps = [], 0
+    bad, steps, stuck_steps = [], 0, 0
     for p in range(plies):
+        stuck_steps += int((prev == 0xFFFF).sum())  # over all n boards, not only the sampled ones
         acts = np.where(prev == 0xFFFF, 0, prev).astype(np.uint16)
         io.upload_actions(acts)
         env.step_device(io, autoreset=True)
@@ -217,7 +228,15 @@ def api_opp_case(seed, color, plies, n, idx):
                 break
             if legal:
                 o.pick()
+            else:  # stuck: the host reset below, and its policy pick
+                o.reset()
+                o.pick()
             steps += 1
+        prev = out["pick"].astype(np.int64)
+        stuck = prev == 0xFFFF
+        if stuck.any() and not bad:
+            env.reset(stuck.astype(np.uint8), states=False)
+            prev[stuck] = env.outputs()["next_action"][stuck]
         if p % 500 == 499 or p == plies - 1:
             b, m = env.boards()
             for i, o in ors.items():
@@ -227,23 +246,86 @@ def api_opp_case(seed, color, plies, n, idx):
                     break
         if bad:
             break
-        prev = out["pick"].astype(np.int64)
     spill = env.spill_info() if color == "BLACK" else None
     io.close()
     env.close()
-    return bad, steps, spill, round(time.time() - t0, 1)
+    return bad, steps, spill, round(time.time() - t0, 1), stuck_steps
 
 
 def api_opp_soak(a):
     n, color = a.boards, a.api_opp
     idx = np.array(sorted(set(range(0, n, 1021)) | set(range(64)) | set(range(n - 64, n))), dtype=np.int64)
     for seed in (0x0A11 + 97 * k for k in range(a.seeds)):
-        bad, steps, spill, secs = api_opp_case(seed, color, a.plies, n, idx)
+        bad, steps, spill, secs, stuck_steps = api_opp_case(seed, color, a.plies, n, idx)
         print(json.dumps({"api_opp_seed": seed, "color": color, "boards": n, "plies": a.plies,
-                          "sampled": len(idx), "board_steps_checked": steps, "mismatches": bad[:8],
-                          "spill": spill, "seconds": secs}), flush=True)
+                          "sampled": len(idx), "board_steps_checked": steps, "stuck_steps": stuck_steps,
+                          "mismatches": bad[:8], "spill": spill, "seconds": secs}), flush=True)
         if bad:
             sys.exit(1)
+
+
+def api_digest_replay(a):
+    """One board of a tests/test_api_digest.py case, step by step: the device loop (an env of
+    board + 1 boards: the boards are independent) against the oracle env, every field of every
+    step; prints the first step that differs and the fields."""
+    import oracle as O
+    from gym_chess_amd.env import BatchedChessEnv
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_api_digest as T
+
+    name, seed, opp, color = next(c for c in T.CASES if c[0] == a.api_digest)
+    i, n, steps = a.board, a.board + 1, min(a.plies, T.STEPS)
+    s, r = T.schedule(seed, [i], steps, threads=1)
+    env = BatchedChessEnv(n, device=0, seed=seed, opponent="random" if opp else "none", player_color=color)
+    io = env.device_io()
+    act_buf = env.device_io(mask=False, obs=False, count=False, pick=True, select=False)
+    o = O.OracleEnv(opponent=opp, agent_white=color == "WHITE", seed=seed, board=i)
+    acts = io.fetch("pick")["pick"].astype(np.uint16)
+    want_a = o.pick()
+    for p in range(steps):
+        if int(acts[i]) != want_a:
+            print(json.dumps({"case": name, "board": i, "step": p, "field": "carried action", "device": int(acts[i]),
+                              "oracle": want_a}))
+            sys.exit(1)
+        acts[i] = T.choose([want_a], s[p], r[p])[0]
+        act_buf.upload_actions(acts)
+        env.step_device(io, actions=act_buf.ptr["pick"], autoreset=True)
+        out = io.fetch()
+        rc, rw, dn, why = o.step(int(acts[i]))
+        if rc == 1:
+            dn, why = 1, 5
+        if dn:
+            o.reset()
+        legal = sorted(o.moves())
+        pick = 0xFFFF
+        if legal:
+            pick = legal[O.policy_index(seed, i, o.draw, len(legal))]
+            o.pick()
+        want = {"reward": rw, "done": dn, "reason": why, "pick": pick, "count": len(legal),
+                "mask": T.mask_words(legal).tolist(), "obs": o.state()[0].tolist()}
+        got = {k: out[k][i].tolist() for k in want}
+        diff = [k for k in want if want[k] != got[k]]
+        if diff:
+            print(json.dumps({"case": name, "board": i, "step": p, "action": int(acts[i]), "fields": diff,
+                              "device": {k: got[k] for k in diff}, "oracle": {k: want[k] for k in diff}}))
+            sys.exit(1)
+        acts = out["pick"].copy()
+        if not legal:
+            o.reset()
+            want_a = o.pick()
+            stuck = np.zeros(n, dtype=np.uint8)
+            stuck[i] = 1
+            env.reset(stuck, states=False)
+            acts[i] = env.outputs()["next_action"][i]
+        else:
+            want_a = pick
+        acts[acts == 0xFFFF] = 0  # the other boards only keep the launch shape
+    b, m = env.boards()
+    ob, om = o.state()
+    ok = bool((b[i] == ob).all() and list(m[i]) == list(om))
+    print(json.dumps({"case": name, "board": i, "steps": steps, "equal": ok}))
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":
