@@ -81,16 +81,8 @@ namespace gcf = gc::fide;
 #define BLOCK 256
 
 // ----------------------------------------------------------------------------- errors
-static thread_local std::string g_err;
-static int fail(const std::string& m) {
-    g_err = m;
-    return -1;
-}
-#define HIPCHK(x)                                                                   \
-    do {                                                                            \
-        hipError_t e_ = (x);                                                        \
-        if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#include "gc_host_base.h"
+#include "gc_host_hip.h"
 
 extern "C" const char* gc_last_error(void) { return g_err.c_str(); }
 extern "C" int gc_version(void) { return GC_ABI_VERSION; }
@@ -4607,2772 +4599,12 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 }
 
 
-// ----------------------------------------------------------------------------- host side
-static inline int grid_for(int n) { return (n + BLOCK - 1) / BLOCK; }
-
-template <class T>
-static int dalloc(T** p, size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
-    return 0;
-}
-
-struct gc_engine {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int cap_n = 0, cap_list = 0;
-    u64* bb = nullptr; u32* meta = nullptr;       // input states
-    u64* bb2 = nullptr; u32* meta2 = nullptr;     // output states
-    // The host-facing buffers of one call are views into ONE device block (dio), laid out for
-    // the call's n by engine_layout, mirrored by a pinned host block (hio): a call stages its
-    // inputs with one host-to-device copy and returns its outputs with one copy back (a
-    // single-board call is latency-bound: every copy is a round trip)
-    uint8_t* dio = nullptr; uint8_t* hio = nullptr; size_t io_cap = 0;
-    int8_t* mbox = nullptr; uint8_t* m8 = nullptr; uint8_t* side = nullptr;
-    uint16_t* acts = nullptr; int32_t* i32a = nullptr; int32_t* i32b = nullptr;
-    uint16_t* list = nullptr; uint64_t* u64o = nullptr;
-    int rules = 0;  // 0 reference (lib.rs), 1 FIDE (gc_fide.h)
-    // small calls (a layout within ENGINE_ZC_BYTES) stage in host-mapped coherent memory that
-    // the kernels read and write directly: one launch and no copy per call, where the
-    // staged form paid a copy each way (two more dispatches) around it
-    uint8_t* zc = nullptr; uint8_t* zcd = nullptr; bool zc_on = false;
-    // one-position calls under the reference rules go to the engine server (k_engine_server)
-    struct EngBox* srv = nullptr; struct EngBox* srv_d = nullptr;
-    hipStream_t srv_stream = nullptr;
-    uint32_t srv_seq = 0, srv_launch = 0, srv_next_launch = 0;
-    // one call at a time per engine: ctypes releases the GIL, and a call's staging buffers
-    // and the server's mailbox are the engine's own
-    std::mutex mu;
-};
-#define ENGINE_ZC_BYTES 65536
-// byte offsets of the views for n boards and a list capacity lc (256-B aligned)
-struct EngineLayout {
-    size_t mbox, m8, side, acts, i32a, i32b, list, end;
-};
-static EngineLayout engine_offsets(size_t n, size_t lc) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    EngineLayout o;
-    o.mbox = 0;
-    o.m8 = up(o.mbox + 64 * n);
-    o.side = up(o.m8 + 8 * n);
-    o.acts = up(o.side + n);
-    o.i32a = up(o.acts + 2 * n);
-    o.i32b = up(o.i32a + 4 * n);
-    o.list = up(o.i32b + 4 * n);
-    o.end = up(o.list + 2 * lc * n);
-    return o;
-}
-static EngineLayout engine_layout(gc_engine* e, int n, int lc, uint8_t* base) {
-    EngineLayout o = engine_offsets((size_t)n, (size_t)lc);
-    e->mbox = reinterpret_cast<int8_t*>(base + o.mbox);
-    e->m8 = base + o.m8;
-    e->side = base + o.side;
-    e->acts = reinterpret_cast<uint16_t*>(base + o.acts);
-    e->i32a = reinterpret_cast<int32_t*>(base + o.i32a);
-    e->i32b = reinterpret_cast<int32_t*>(base + o.i32b);
-    e->list = reinterpret_cast<uint16_t*>(base + o.list);
-    return o;
-}
-static bool engine_zc_enabled() {
-    static const bool off = getenv("GC_ENGINE_ZC") && atoi(getenv("GC_ENGINE_ZC")) == 0;  // A/B
-    return !off;
-}
-
-static void engine_free_bufs(gc_engine* e) {
-    void* ps[] = {e->bb, e->meta, e->bb2, e->meta2, e->dio, e->u64o};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    if (e->hio) (void)hipHostFree(e->hio);
-    if (e->zc) (void)hipHostFree(e->zc);
-    e->zc = nullptr; e->zcd = nullptr; e->zc_on = false;
-    e->bb = nullptr; e->meta = nullptr; e->bb2 = nullptr; e->meta2 = nullptr; e->dio = nullptr; e->hio = nullptr;
-    e->mbox = nullptr; e->m8 = nullptr; e->side = nullptr; e->acts = nullptr; e->i32a = nullptr; e->i32b = nullptr;
-    e->list = nullptr; e->u64o = nullptr;
-    e->cap_n = 0; e->cap_list = 0; e->io_cap = 0;
-}
-
-static int engine_reserve(gc_engine* e, int n, int listcap) {
-    if (n <= e->cap_n && listcap <= e->cap_list) return 0;
-    int nn = n > e->cap_n ? n : e->cap_n, lc = listcap > e->cap_list ? listcap : e->cap_list;
-    engine_free_bufs(e);
-    const size_t io = engine_offsets((size_t)nn, (size_t)lc).end;
-    if (dalloc(&e->bb, (size_t)NBB * nn) || dalloc(&e->meta, nn) || dalloc(&e->bb2, (size_t)NBB * nn) ||
-        dalloc(&e->meta2, nn) || dalloc(&e->dio, io) || dalloc(&e->u64o, nn))
-        return -1;
-    hipError_t he = hipHostMalloc((void**)&e->hio, io, hipHostMallocDefault);
-    if (he != hipSuccess) return fail(std::string("hipHostMalloc: ") + hipGetErrorString(he));
-    e->io_cap = io;
-    e->cap_n = nn;
-    e->cap_list = lc;
-    return 0;
-}
-// one call's staging: the inputs present (side / acts may be null) into the pinned block, one
-// copy to the device; the views laid out for (n, lc)
-static int engine_stage(gc_engine* e, int n, int lc, const int8_t* boards, const uint8_t* meta, const uint8_t* side,
-                        const uint16_t* acts, EngineLayout& o) {
-    e->zc_on = engine_zc_enabled() && engine_offsets((size_t)n, (size_t)lc).end <= ENGINE_ZC_BYTES;
-    if (e->zc_on && !e->zc) {
-        HIPCHK(hipHostMalloc((void**)&e->zc, ENGINE_ZC_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->zcd, e->zc, 0));
-    }
-    uint8_t* h = e->zc_on ? e->zc : e->hio;
-    o = engine_layout(e, n, lc, e->zc_on ? e->zcd : e->dio);
-    std::memcpy(h + o.mbox, boards, (size_t)64 * n);
-    std::memcpy(h + o.m8, meta, (size_t)8 * n);
-    size_t end = o.m8 + (size_t)8 * n;
-    if (side) { std::memcpy(h + o.side, side, (size_t)n); end = o.side + n; }
-    if (acts) { std::memcpy(h + o.acts, acts, (size_t)2 * n); end = o.acts + (size_t)2 * n; }
-    if (!e->zc_on) HIPCHK(hipMemcpyAsync(e->dio, e->hio, end, hipMemcpyHostToDevice, e->stream));
-    return 0;
-}
-// the byte range [a, b) of the device block back into the pinned one, then wait (a small
-// call's outputs are already in host memory: only the wait, and the range into hio)
-static int engine_fetch(gc_engine* e, size_t a, size_t b) {
-    if (!e->zc_on) HIPCHK(hipMemcpyAsync(e->hio + a, e->dio + a, b - a, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->zc_on) std::memcpy(e->hio + a, e->zc + a, b - a);
-    return 0;
-}
-
-static int check_boards(int n, const int8_t* boards) {
-    for (size_t k = 0; k < (size_t)64 * n; k++)
-        if (boards[k] < -6 || boards[k] > 6) return fail("piece id out of range [-6, 6] at index " + std::to_string(k));
-    return 0;
-}
-
-// side: staged when given, and the side to move of the import unless side_import is false
-static int engine_upload(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta, const uint8_t* side,
-                         EngineLayout& o, int lc = 1, const uint16_t* acts = nullptr, bool side_import = true) {
-    if (n <= 0) return fail("n must be > 0");
-    if (!boards || !meta) return fail("null boards/meta");
-    if (check_boards(n, boards)) return -1;
-    HIPCHK(hipSetDevice(e->device));
-    if (engine_stage(e, n, lc, boards, meta, side, acts, o)) return -1;
-    if (!side_import) side = nullptr;
-    SoA st{e->bb, e->meta, n};
-    if (e->rules) k_fimport<<<grid_for(n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, side ? e->side : nullptr, st);
-    else k_import<<<grid_for(n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, side ? e->side : nullptr, st);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-static void engine_export(gc_engine* e, SoA st) {
-    if (e->rules) k_fexport<<<grid_for(st.n), BLOCK, 0, e->stream>>>(st, e->mbox, e->m8);
-    else k_export<<<grid_for(st.n), BLOCK, 0, e->stream>>>(st, e->mbox, e->m8);
-}
-
-// rules 0: the reference's (default); 1: FIDE (gc_fide.h; meta8[7] = en-passant file + 1)
-extern "C" int gc_engine_set_rules(gc_engine* e, int rules) {
-    if (!e) return fail("null engine");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (rules != 0 && rules != 1) return fail("rules must be 0 (reference) or 1 (fide)");
-    e->rules = rules;
-    return 0;
-}
-
-extern "C" int gc_engine_create(int device, gc_engine** out) {
-    if (!out) return fail("null out pointer");
-    int nd = 0;
-    HIPCHK(hipGetDeviceCount(&nd));
-    if (device < 0 || device >= nd) return fail("device index out of range");
-    gc_engine* e = new gc_engine();
-    e->device = device;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    if (engine_reserve(e, 256, 256)) { delete e; return -1; }
-    *out = e;
-    return 0;
-}
-
-// ---- resident servers at process exit: a server wave exits after SRV_IDLE_MS without a
-// request, so a process that ends right after its last call (without destroying the env or
-// engine) could end with the wave still resident.  Every running server is registered here;
-// an atexit handler asks each to QUIT through its host-mapped mailbox and waits (host memory
-// only, no HIP call: the runtime may be tearing down) until it has marked its exit.
-struct SrvReg {
-    u32 *req_seq, *op, *exited;      // the mailbox (host-mapped)
-    const u32 *seq, *launch;         // the owner's last served sequence number and launch id
-};
-static std::mutex g_srvreg_mu;
-static std::vector<std::pair<const void*, SrvReg>> g_srvreg;
-static void srv_quit_all() {
-    std::lock_guard<std::mutex> lk(g_srvreg_mu);
-    const bool log = getenv("GC_SRV_EXIT_LOG") != nullptr;  // (tests: which servers this stopped)
-    for (auto& it : g_srvreg) {
-        const SrvReg& r = it.second;
-        if (!*r.launch || __atomic_load_n(r.exited, __ATOMIC_ACQUIRE) == *r.launch) continue;
-        __atomic_store_n(r.op, (u32)SRV_QUIT, __ATOMIC_RELAXED);
-        __atomic_store_n(r.req_seq, *r.seq + 1, __ATOMIC_RELEASE);
-        const auto t0 = std::chrono::steady_clock::now();
-        while (__atomic_load_n(r.exited, __ATOMIC_ACQUIRE) != *r.launch &&
-               std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(2 * SRV_IDLE_MS)) {
-        }
-        if (log)
-            fprintf(stderr, "gymchess: server of %p %s at exit\n", it.first,
-                    __atomic_load_n(r.exited, __ATOMIC_ACQUIRE) == *r.launch ? "stopped" : "did not answer");
-    }
-    g_srvreg.clear();
-}
-static void srv_register(const void* owner, const SrvReg& r) {
-    std::lock_guard<std::mutex> lk(g_srvreg_mu);
-    static bool hooked = false;
-    if (!hooked) {
-        std::atexit(srv_quit_all);
-        hooked = true;
-    }
-    for (auto& it : g_srvreg)
-        if (it.first == owner) return;
-    g_srvreg.emplace_back(owner, r);
-}
-static void srv_unregister(const void* owner) {
-    std::lock_guard<std::mutex> lk(g_srvreg_mu);
-    for (size_t k = 0; k < g_srvreg.size(); k++)
-        if (g_srvreg[k].first == owner) {
-            g_srvreg.erase(g_srvreg.begin() + (long)k);
-            return;
-        }
-}
-
-// ---- one resident server per device.  A resident wave holds its hardware
-// queue until it exits, and HIP maps a process's streams onto GPU_MAX_HW_QUEUES (4 on the box)
-// queues: with more streams than that, work on a stream that shares a queue with a resident
-// server waits behind it until it idles out (SRV_IDLE_MS) -- ~50 ms per call for single-board
-// envs stepped round-robin, or env.step mixed with ChessEngine calls.  So at most one server
-// runs per device: a request to another owner's server, and every launch of this library on
-// the device (SRV_QUIESCE, devsrv_quiesce), first stops the resident one (QUIT, its stream
-// drained).  The slot's mutex is held for a whole server call (lock order: an engine's own
-// mutex, then the slot's), so a server's state is only touched under it.
-#define GC_MAX_DEVICES 64
-struct DevSrv {
-    std::recursive_mutex mu;
-    std::atomic<void*> owner{nullptr};  // the env / engine whose server may be resident
-    int (*stop)(void*) = nullptr;       // its stop (QUIT + drain)
-};
-static DevSrv g_devsrv[GC_MAX_DEVICES];
-static DevSrv& devsrv(int dev) { return g_devsrv[(unsigned)dev % GC_MAX_DEVICES]; }
-// (held: s.mu)
-static int devsrv_stop_locked(DevSrv& s) {
-    void* o = s.owner.exchange(nullptr, std::memory_order_acq_rel);
-    return o ? s.stop(o) : 0;
-}
-// (Lock-free when no server is resident.  Callers on other threads may claim the slot between
-// this check and their own launch: that launch then queues behind the new server until the
-// server stops -- at the next call of another owner, or by itself after SRV_IDLE_MS without a
-// request -- a delay, never a wrong result.)
-static int devsrv_quiesce(int dev) {
-    DevSrv& s = devsrv(dev);
-    if (!s.owner.load(std::memory_order_acquire)) return 0;
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    return devsrv_stop_locked(s);
-}
-// (held: s.mu) the slot for `owner`: another owner's server is stopped first
-static int devsrv_claim(DevSrv& s, void* owner, int (*stop)(void*)) {
-    void* o = s.owner.load(std::memory_order_acquire);
-    if (o && o != owner && devsrv_stop_locked(s)) return -1;
-    s.stop = stop;
-    s.owner.store(owner, std::memory_order_release);
-    return 0;
-}
-static void devsrv_release(DevSrv& s, void* owner) {
-    void* o = owner;
-    s.owner.compare_exchange_strong(o, nullptr, std::memory_order_acq_rel);
-}
-
-// ---- the engine server's host side (the single-board server's protocol, srv_call)
-static bool eng_srv_enabled() {
-    static const bool off = getenv("GC_ENGINE_SERVER") && atoi(getenv("GC_ENGINE_SERVER")) == 0;  // A/B
-    return !off;
-}
-static int eng_srv_stop(gc_engine* e) {
-    DevSrv& s = devsrv(e->device);
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    devsrv_release(s, e);
-    if (!e->srv_launch) return 0;
-    EngBox* b = e->srv;
-    __atomic_store_n(&b->op, (u32)SRV_QUIT, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->req_seq, e->srv_seq + 1, __ATOMIC_RELEASE);  // (never served: QUIT)
-    const hipError_t he = hipStreamSynchronize(e->srv_stream);
-    __atomic_store_n(&b->req_seq, e->srv_seq, __ATOMIC_RELEASE);
-    e->srv_launch = 0;
-    if (he != hipSuccess) return fail(std::string("engine server: ") + hipGetErrorString(he));
-    return 0;
-}
-// one op on one position; the response lands in e->srv
-static int eng_srv_stop_v(void* e) { return eng_srv_stop(static_cast<gc_engine*>(e)); }
-static int eng_srv_call(gc_engine* e, int op, const int8_t* board, const uint8_t* meta, bool white, int arg) {
-    HIPCHK(hipSetDevice(e->device));
-    DevSrv& s = devsrv(e->device);
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    if (devsrv_claim(s, e, eng_srv_stop_v)) return -1;
-    if (!e->srv) {
-        HIPCHK(hipHostMalloc((void**)&e->srv, sizeof(EngBox), hipHostMallocMapped | hipHostMallocCoherent));
-        memset(e->srv, 0, sizeof(EngBox));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->srv_d, e->srv, 0));
-        HIPCHK(hipStreamCreateWithFlags(&e->srv_stream, hipStreamNonBlocking));
-    }
-    EngBox* b = e->srv;
-    const u32 seq = e->srv_seq + 1;
-    memcpy(b->board, board, 64);
-    memcpy(b->meta, meta, 8);
-    __atomic_store_n(&b->op, (u32)op, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->white, white ? 1u : 0u, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->arg, (u32)arg, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->req_seq, seq, __ATOMIC_RELEASE);  // last
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned k = 0;; k++) {
-        if (!e->srv_launch || __atomic_load_n(&b->exited, __ATOMIC_ACQUIRE) == e->srv_launch) {
-            if (e->srv_launch) HIPCHK(hipStreamSynchronize(e->srv_stream));  // drained (idle exit)
-            e->srv_launch = ++e->srv_next_launch;
-            srv_register(e, SrvReg{&b->req_seq, &b->op, &b->exited, &e->srv_seq, &e->srv_launch});
-            k_engine_server<<<1, 64, 0, e->srv_stream>>>(e->srv_d, e->srv_seq, e->srv_launch);
-            HIPCHK(hipGetLastError());
-        }
-        if (__atomic_load_n(&b->resp_seq, __ATOMIC_ACQUIRE) == seq) break;
-        if ((k & 1023) == 1023) {
-            const hipError_t q = hipStreamQuery(e->srv_stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(std::string("engine server: ") + hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-                (void)eng_srv_stop(e);
-                return fail("engine server: no answer within 10 s");
-            }
-        }
-    }
-    e->srv_seq = seq;
-    return 0;
-}
-static bool eng_srv_use(const gc_engine* e, int n) { return n == 1 && !e->rules && eng_srv_enabled(); }
-
-extern "C" int gc_engine_destroy(gc_engine* e) {
-    if (!e) return 0;
-    (void)hipSetDevice(e->device);
-    (void)eng_srv_stop(e);
-    srv_unregister(e);
-    if (e->srv_stream) (void)hipStreamDestroy(e->srv_stream);
-    if (e->srv) (void)hipHostFree(e->srv);
-    (void)hipStreamSynchronize(e->stream);
-    engine_free_bufs(e);
-    (void)hipStreamDestroy(e->stream);
-    delete e;
-    return 0;
-}
-
-extern "C" int gc_engine_get_possible_moves(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta,
-                                            const uint8_t* player_white, int attack, uint16_t* moves, int cap,
-                                            int32_t* counts) {
-    if (!e || !moves || !counts || !player_white) return fail("null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (cap <= 0) return fail("cap must be > 0");
-    if (eng_srv_use(e, n) && cap <= ENG_SRV_CAP) {
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(1, boards)) return -1;
-        if (eng_srv_call(e, ENG_LIST, boards, meta, player_white[0] != 0, attack ? 1 : 0)) return -1;
-        const int c = (int)e->srv->count;
-        memcpy(moves, e->srv->moves, (size_t)2 * (c < cap ? c : cap));
-        counts[0] = c;
-        return 0;
-    }
-    if (devsrv_quiesce(e->device) || engine_reserve(e, n, cap)) return -1;
-    EngineLayout o;
-    if (e->rules) {
-        if (engine_upload(e, n, boards, meta, player_white, o, cap)) return -1;
-        k_flist<<<grid_for(n), BLOCK, 0, e->stream>>>(SoA{e->bb, e->meta, n}, attack ? 1 : 0, cap, e->list, e->i32a);
-    } else {  // one launch: import + list
-        if (n <= 0) return fail("n must be > 0");
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(n, boards)) return -1;
-        HIPCHK(hipSetDevice(e->device));
-        if (engine_stage(e, n, cap, boards, meta, player_white, nullptr, o)) return -1;
-        k_list_mb<<<grid_for(n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, e->side, n, attack ? 1 : 0, cap, e->list, e->i32a);
-    }
-    HIPCHK(hipGetLastError());
-    if (engine_fetch(e, o.i32a, o.list + (size_t)2 * cap * n)) return -1;
-    std::memcpy(moves, e->hio + o.list, (size_t)2 * cap * n);
-    std::memcpy(counts, e->hio + o.i32a, (size_t)4 * n);
-    return 0;
-}
-
-extern "C" int gc_engine_get_castle_moves(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta,
-                                          const uint8_t* player_white, uint16_t* moves, int32_t* counts) {
-    if (!e || !moves || !counts || !player_white) return fail("null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (eng_srv_use(e, n)) {
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(1, boards)) return -1;
-        if (eng_srv_call(e, ENG_CASTLE, boards, meta, player_white[0] != 0, 0)) return -1;
-        const u32 c = e->srv->count;
-        int k = 0;  // reference order (QS then KS, lib.rs:992,1011)
-        if (c & 2u) moves[k++] = A_QSW;
-        if (c & 1u) moves[k++] = A_KSW;
-        if (c & 8u) moves[k++] = A_QSB;
-        if (c & 4u) moves[k++] = A_KSB;
-        counts[0] = k;
-        return 0;
-    }
-    if (devsrv_quiesce(e->device) || engine_reserve(e, n, 2)) return -1;
-    EngineLayout o;
-    if (engine_upload(e, n, boards, meta, player_white, o, 2)) return -1;
-    std::vector<u64> mask(e->rules ? (size_t)65 * n : 0);
-    if (e->rules) {
-        u64* dmask = nullptr;
-        if (dalloc(&dmask, (size_t)65 * n)) return -1;
-        k_fmask<<<grid_for(n), BLOCK, 0, e->stream>>>(SoA{e->bb, e->meta, n}, dmask, nullptr);
-        hipError_t le = hipGetLastError();
-        hipError_t ce = hipMemcpyAsync(mask.data(), dmask, (size_t)8 * 65 * n, hipMemcpyDeviceToHost, e->stream);
-        hipError_t se = hipStreamSynchronize(e->stream);
-        (void)hipFree(dmask);
-        if (le != hipSuccess || ce != hipSuccess || se != hipSuccess) return fail("castle mask kernel failed");
-    } else {  // the castle word per board into the layout's int32 row
-        k_castle_word<<<grid_for(n), BLOCK, 0, e->stream>>>(SoA{e->bb, e->meta, n}, e->i32a);
-        HIPCHK(hipGetLastError());
-        if (engine_fetch(e, o.i32a, o.i32a + (size_t)4 * n)) return -1;
-    }
-    for (int i = 0; i < n; i++) {  // unpack in reference order (QS then KS, lib.rs:992,1011)
-        const u64 c = e->rules ? mask[(size_t)65 * i + 64] : (u64)reinterpret_cast<const int32_t*>(e->hio + o.i32a)[i];
-        int k = 0;
-        uint16_t* o = moves + 2 * (size_t)i;
-        if (c & (1ull << 1)) o[k++] = A_QSW;
-        if (c & (1ull << 0)) o[k++] = A_KSW;
-        if (c & (1ull << 3)) o[k++] = A_QSB;
-        if (c & (1ull << 2)) o[k++] = A_KSB;
-        counts[i] = k;
-    }
-    return 0;
-}
-
-extern "C" int gc_engine_next_state(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta,
-                                    const uint8_t* player_white, const uint16_t* actions, int8_t* out_boards,
-                                    uint8_t* out_meta, int32_t* rewards, int32_t* status) {
-    if (!e || !player_white || !actions || !out_boards || !out_meta || !rewards || !status) return fail("null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    for (int i = 0; i < n; i++)
-        if (actions[i] > A_QSB) return fail("action out of range at index " + std::to_string(i));
-    if (eng_srv_use(e, n)) {
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(1, boards)) return -1;
-        if (eng_srv_call(e, ENG_NEXT, boards, meta, player_white[0] != 0, actions[0])) return -1;
-        memcpy(out_boards, e->srv->out_board, 64);
-        memcpy(out_meta, e->srv->out_meta, 8);
-        rewards[0] = e->srv->reward;
-        status[0] = e->srv->status;
-        return 0;
-    }
-    if (devsrv_quiesce(e->device) || engine_reserve(e, n, 1)) return -1;
-    // FIDE: the player argument is the side to move; reference: it only steers next_state's
-    // promotion colour and rights logic (lib.rs:679-784), the state keeps current_player
-    // the import reads side only under FIDE (the player argument is the side to move there)
-    EngineLayout o;
-    if (e->rules) {
-        if (engine_upload(e, n, boards, meta, player_white, o, 1, actions)) return -1;
-        SoA in{e->bb, e->meta, n}, out{e->bb2, e->meta2, n};
-        k_fnext_state<<<grid_for(n), BLOCK, 0, e->stream>>>(in, e->acts, out, e->i32a, e->i32b);
-        HIPCHK(hipGetLastError());
-        engine_export(e, out);
-    } else {  // one launch: import + next_state + export, in place on the staged mailbox
-        if (n <= 0) return fail("n must be > 0");
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(n, boards)) return -1;
-        HIPCHK(hipSetDevice(e->device));
-        if (engine_stage(e, n, 1, boards, meta, player_white, actions, o)) return -1;
-        k_next_state_mb<<<grid_for(n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, e->side, e->acts, n, e->i32a, e->i32b);
-    }
-    HIPCHK(hipGetLastError());
-    if (engine_fetch(e, 0, o.i32b + (size_t)4 * n)) return -1;
-    std::memcpy(out_boards, e->hio + o.mbox, (size_t)64 * n);
-    std::memcpy(out_meta, e->hio + o.m8, (size_t)8 * n);
-    std::memcpy(rewards, e->hio + o.i32a, (size_t)4 * n);
-    std::memcpy(status, e->hio + o.i32b, (size_t)4 * n);
-    return 0;
-}
-
-extern "C" int gc_engine_update_state(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta,
-                                      int8_t* out_boards, uint8_t* out_meta) {
-    if (!e || !out_boards || !out_meta) return fail("null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (eng_srv_use(e, n)) {
-        if (!boards || !meta) return fail("null boards/meta");
-        if (check_boards(1, boards)) return -1;
-        if (eng_srv_call(e, ENG_UPDATE, boards, meta, false, 0)) return -1;
-        memcpy(out_boards, e->srv->out_board, 64);
-        memcpy(out_meta, e->srv->out_meta, 8);
-        return 0;
-    }
-    if (devsrv_quiesce(e->device) || engine_reserve(e, n, 1)) return -1;
-    EngineLayout o;
-    if (engine_upload(e, n, boards, meta, nullptr, o)) return -1;
-    SoA st{e->bb, e->meta, n};
-    if (e->rules) k_fupdate_state<<<grid_for(n), BLOCK, 0, e->stream>>>(st);
-    else k_update_state<<<grid_for(n), BLOCK, 0, e->stream>>>(st);
-    HIPCHK(hipGetLastError());
-    engine_export(e, st);
-    HIPCHK(hipGetLastError());
-    if (engine_fetch(e, 0, o.m8 + (size_t)8 * n)) return -1;
-    std::memcpy(out_boards, e->hio + o.mbox, (size_t)64 * n);
-    std::memcpy(out_meta, e->hio + o.m8, (size_t)8 * n);
-    return 0;
-}
-
-// depth-3 subtrees as depth-2 ones: the level below `leaf` is materialised chunk by chunk
-// (it is ~30x larger) and its nodes run in order of their move counts, so the leaf kernel's
-// one remaining loop has (nearly) equal trip counts across a wave -- with depth-3 subtrees
-// the inner loop's trip count varied per lane (PMC: ~60 % lane utilisation).
-// leaf-kernel time of the split pass (gc_perft_leaf_stats): HIP events around every
-// leaf launch (k_perft2_val / k_perft2_rec), on the stream it runs on; summed once the pass has synchronised
-static std::mutex g_leaf_mu;
-static uint64_t g_leaf_launches = 0, g_leaf_subtrees = 0, g_leaf_records = 0;
-static double g_leaf_ms = 0.0;
-
-static int perft_split_leaves(hipStream_t st, SoA leaf, uint64_t* leaf_out) {
-    // parents per chunk 2^21 and up to 2^27 children (7.5 GiB of boards); GC_PERFT_CHUNK=k
-    // (A/B): 2^k parents, 2^(k+6) children (2^20 / 2^22 measured 1.92 / 1.83 vs 1.93e12)
-    static const int chunk_log2 = getenv("GC_PERFT_CHUNK") ? atoi(getenv("GC_PERFT_CHUNK")) : 21;
-    // (the lead word holds a sorted position in RUN_LEN_SHIFT bits)
-    if (chunk_log2 < 10 || chunk_log2 + 6 > RUN_LEN_SHIFT)
-        return fail("GC_PERFT_CHUNK must be in [10, 21] (2^k parents per chunk)");
-    const int64_t cap = (int64_t)1 << (chunk_log2 + 6);
-    int chunk = 1 << chunk_log2;
-    std::vector<hipEvent_t> evs;  // pairs around the leaf launches
-    uint64_t subtrees = 0, records = 0;  // subtrees counted by the leaf kernel, of records made
-    // GC_PERFT_DEDUP=0 (per call; tests): every record counted, transpositions too
-    const char* dd = getenv("GC_PERFT_DEDUP");
-    const bool dedup = !(dd && dd[0] == '0');
-    int32_t *kc = nullptr, *offs = nullptr;
-    uint8_t* bins = nullptr;
-    u32 *hist = nullptr, *hbase = nullptr;
-    const int max_blk = (chunk + BLOCK - 1) / BLOCK;
-    const int max_dblk = (int)((cap + DEDUP_BLOCK * DEDUP_R - 1) / (DEDUP_BLOCK * DEDUP_R));  // the histograms' blocks
-    const int hist_n = SPLIT_BINS * (dedup && max_dblk > max_blk ? max_dblk : max_blk);
-    Node64* cr = nullptr;
-    // the transposition pass: the records in expansion order; the sort's keys / values (16 B per
-    // record), reused after it for the members' (leader, parent) pairs; the lead words; the
-    // placed leaders' sorted positions
-    Node64* cre = nullptr;
-    u32* kv = nullptr;
-    u32* leadw = nullptr;
-    u32* spos = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    int rc = 0;
-    std::string err;
-    auto done = [&]() {
-        void* ps[] = {kc, offs, cr, tmp, bins, hist, hbase, cre, kv, leadw, spos};
-        for (void* q : ps) (void)hipFree(q);
-        for (hipEvent_t ev : evs) (void)hipEventDestroy(ev);
-    };
-    if (dalloc(&kc, leaf.n) || dalloc(&offs, chunk) || dalloc(&cr, cap) || dalloc(&bins, cap) ||
-        dalloc(&hist, (size_t)hist_n) || dalloc(&hbase, (size_t)hist_n) ||
-        (dedup && (dalloc(&cre, cap) || dalloc(&kv, 4 * cap) || dalloc(&leadw, cap) || dalloc(&spos, cap)))) {
-        done();
-        return -1;
-    }
-    {  // scratch for the largest scan and sort of a chunk
-        size_t b1 = 0, b2 = 0, b3 = 0;
-        hipError_t he = hipcub::DeviceScan::ExclusiveSum(nullptr, b1, kc, offs, chunk, st);
-        if (he == hipSuccess) he = hipcub::DeviceScan::ExclusiveSum(nullptr, b2, hist, hbase, hist_n, st);
-        if (he == hipSuccess && dedup)
-            he = hipcub::DeviceRadixSort::SortPairs(nullptr, b3, kv, kv + cap, kv + 2 * cap, kv + 3 * cap, (int)cap, 0, 32, st);
-        tmp_bytes = b1 > b2 ? b1 : b2;
-        tmp_bytes = tmp_bytes > b3 ? tmp_bytes : b3;
-        if (he != hipSuccess) { done(); return fail(std::string("perft split: ") + hipGetErrorString(he)); }
-        if (dalloc((char**)&tmp, tmp_bytes)) { done(); return -1; }
-    }
-    k_count_children<int32_t><<<grid_for(leaf.n), BLOCK, 0, st>>>(leaf, kc);
-    for (int a = 0; a < leaf.n && rc == 0;) {
-        int c = leaf.n - a < chunk ? leaf.n - a : chunk;
-        size_t tb = tmp_bytes;
-        hipError_t he = hipcub::DeviceScan::ExclusiveSum(tmp, tb, kc + a, offs, c, st);
-        int32_t lo = 0, lc = 0;
-        if (he == hipSuccess) he = hipMemcpyAsync(&lo, offs + c - 1, 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(&lc, kc + a + c - 1, 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) { err = std::string("perft split: ") + hipGetErrorString(he); rc = -1; break; }
-        int64_t total = (int64_t)lo + lc;
-        if (total > cap) { chunk /= 2; continue; }  // an unusually bushy chunk: halve and retry
-        he = hipMemsetAsync(leaf_out + a, 0, (size_t)8 * c, st);  // the parents' sums
-        if (he != hipSuccess) { err = std::string("perft split: ") + hipGetErrorString(he); rc = -1; break; }
-        unsigned long long* psum = reinterpret_cast<unsigned long long*>(leaf_out + a);
-        if (total > 0 && dedup) {  // transpositions merged, the leaders binned and placed in order
-            const int n = (int)total;
-            const int nbd = (n + DEDUP_BLOCK * DEDUP_R - 1) / (DEDUP_BLOCK * DEDUP_R);
-            k_expand_range_rec<<<grid_for(c), BLOCK, 0, st>>>(leaf, a, c, offs, cre);
-            u32* const keys = kv;
-            u32* const vals = kv + cap;
-            u32* const keys2 = kv + 2 * cap;
-            u32* const vals2 = kv + 3 * cap;
-            uint2* const fw = reinterpret_cast<uint2*>(kv);  // after the sort: over keys | vals
-            k_dedup_keys<<<grid_for(n), BLOCK, 0, st>>>(cre, n, keys, vals, bins);
-            tb = tmp_bytes;
-            he = hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys2, vals, vals2, n, 0, 32, st);
-            if (he == hipSuccess) he = hipMemsetAsync(leadw, 0, (size_t)4 * n, st);
-            if (he == hipSuccess) k_dedup_runs_f<<<grid_for(n), BLOCK, 0, st>>>(cre, n, keys2, vals2, leadw, fw);
-            if (he == hipSuccess) k_leader_hist_f<<<nbd, DEDUP_BLOCK, 0, st>>>(n, leadw, bins, hist, nbd);
-            tb = tmp_bytes;
-            if (he == hipSuccess) he = hipcub::DeviceScan::ExclusiveSum(tmp, tb, hist, hbase, SPLIT_BINS * nbd, st);
-            u32 hb = 0, hl = 0;  // the leaders: the last bin's base + its last block's count
-            const size_t last = (size_t)SPLIT_BINS * nbd - 1;
-            if (he == hipSuccess) he = hipMemcpyAsync(&hb, hbase + last, 4, hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipMemcpyAsync(&hl, hist + last, 4, hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) k_place_leaders_f<<<nbd, DEDUP_BLOCK, 0, st>>>(cre, n, bins, leadw, hbase, nbd, cr, spos);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);  // the leaf grid sized to the leaders
-            if (he != hipSuccess) { err = std::string("perft split dedup: ") + hipGetErrorString(he); rc = -1; break; }
-            const int lead_n = (int)(hb + hl);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (hipEventCreate(&e0) == hipSuccess) evs.push_back(e0);
-            if (hipEventCreate(&e1) == hipSuccess) evs.push_back(e1);
-            if (e0 && e1) (void)hipEventRecord(e0, st);
-            k_perft2_val<<<grid_for(lead_n), BLOCK, 0, st>>>(cr, lead_n, psum, n, keys2, fw, spos);
-            if (e0 && e1) (void)hipEventRecord(e1, st);
-            records += (uint64_t)total;
-            subtrees += (uint64_t)lead_n;
-        } else if (total > 0) {  // every record, in move-count order, then read in order
-            const int nb = grid_for(c);
-            k_expand_count<<<nb, BLOCK, 0, st>>>(leaf, a, c, bins, offs, hist, nb);
-            tb = tmp_bytes;
-            he = hipcub::DeviceScan::ExclusiveSum(tmp, tb, hist, hbase, SPLIT_BINS * nb, st);
-            if (he != hipSuccess) { err = std::string("perft split scan: ") + hipGetErrorString(he); rc = -1; break; }
-            k_expand_place<<<nb, BLOCK, 0, st>>>(leaf, a, c, bins, offs, hbase, nb, cr);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (hipEventCreate(&e0) == hipSuccess) evs.push_back(e0);
-            if (hipEventCreate(&e1) == hipSuccess) evs.push_back(e1);
-            if (e0 && e1) (void)hipEventRecord(e0, st);
-            k_perft2_rec<<<grid_for((int)total), BLOCK, 0, st>>>(cr, (int)total, psum);
-            if (e0 && e1) (void)hipEventRecord(e1, st);
-            records += (uint64_t)total;
-            subtrees += (uint64_t)total;
-        }
-        he = hipGetLastError();
-        if (he != hipSuccess) { err = std::string("perft split kernels: ") + hipGetErrorString(he); rc = -1; break; }
-        a += c;
-    }
-    hipError_t he = hipStreamSynchronize(st);  // before the buffers are freed
-    if (rc == 0 && he != hipSuccess) { err = std::string("perft split: ") + hipGetErrorString(he); rc = -1; }
-    if (rc == 0) {
-        double ms = 0.0;
-        for (size_t k = 0; k + 1 < evs.size(); k += 2) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, evs[k], evs[k + 1]) == hipSuccess) ms += t;
-        }
-        std::lock_guard<std::mutex> lk(g_leaf_mu);
-        g_leaf_launches += evs.size() / 2;
-        g_leaf_subtrees += subtrees;
-        g_leaf_records += records;
-        g_leaf_ms += ms;
-    }
-    done();
-    return rc ? fail(err) : 0;
-}
-
-// which leaf pass ran, per pass (gc_perft_path_counts): tests assert that a configuration
-// takes the path it is meant to pin
-static std::atomic<unsigned long long> g_perft_path[4];  // split, sorted, small, fide
-
-// Leaf level: perft(node, rem) of every node of `leaf` (rem <= 3, or few nodes) into out.
-static int perft_leaf(hipStream_t st, SoA ls, int rem, uint64_t* out, int fide) {
-    if (ls.n == 0) return 0;
-    const char* sp = getenv("GC_PERFT_SPLIT");  // per call: tests compare both paths
-    if (!fide && rem == 3 && ls.n >= 65536 && !(sp && sp[0] == '0')) {
-        g_perft_path[0]++;
-        return perft_split_leaves(st, ls, out);
-    }
-    if (!fide && rem >= 2 && ls.n >= 65536) {  // subtrees by root move count
-        int32_t *kc = nullptr, *ks = nullptr, *ix = nullptr, *is = nullptr;
-        void* tmp = nullptr;
-        size_t tb = 0;
-        hipError_t he = hipSuccess;
-        if (dalloc(&kc, ls.n) || dalloc(&ks, ls.n) || dalloc(&ix, ls.n) || dalloc(&is, ls.n)) he = hipErrorOutOfMemory;
-        if (he == hipSuccess) {
-            k_count_children<int32_t><<<grid_for(ls.n), BLOCK, 0, st>>>(ls, kc);
-            k_iota<<<grid_for(ls.n), BLOCK, 0, st>>>(ix, ls.n);
-            he = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kc, ks, ix, is, ls.n, 0, 10, st);
-        }
-        if (he == hipSuccess && dalloc((char**)&tmp, tb) == 0)
-            he = hipcub::DeviceRadixSort::SortPairs(tmp, tb, kc, ks, ix, is, ls.n, 0, 10, st);
-        bool ok = he == hipSuccess && tmp;
-        if (ok) {
-            k_perft_small_perm<<<grid_for(ls.n), BLOCK, 0, st>>>(ls, is, rem, out);
-            he = hipStreamSynchronize(st);  // before the temporaries are freed
-        }
-        (void)hipFree(tmp); (void)hipFree(kc); (void)hipFree(ks); (void)hipFree(ix); (void)hipFree(is);
-        if (he != hipSuccess) return fail(std::string("perft sort: ") + hipGetErrorString(he));
-        if (ok) { g_perft_path[1]++; return 0; }
-    }
-    g_perft_path[fide ? 3 : 2]++;
-    if (fide) k_fperft_small<<<grid_for(ls.n), BLOCK, 0, st>>>(ls, rem, out);
-    else k_perft_small<<<grid_for(ls.n), BLOCK, 0, st>>>(ls, rem, out);
-    return 0;
-}
-
-// Children materialised per chunk of parents: <= PERFT_LEVEL_CAP nodes (60 B each plus
-// 24 B of counts / offsets / values, ~11 GiB at 2^27) so any depth fits HBM; the split-leaf
-// pass below holds its own <= 2^27-child chunk.  GC_PERFT_LEVEL_CAP (per call) lowers it so
-// tests drive the chunked path at small sizes.
-static const int64_t PERFT_LEVEL_CAP = (int64_t)1 << 27;
-
-// out[i] = perft(nodes[i], rem).  While more than 3 plies remain, or while there are too few
-// subtrees to fill the chip, the nodes are expanded into their children on the device
-// (count, exclusive scan in 64 bits, write) and the children recursed on, one chunk of
-// parents at a time when the level would not fit; the parents' values are the sums of their
-// children's.  Sizes are 64-bit throughout: a level's child total may pass 2^31.
-static int perft_nodes(hipStream_t st, SoA nodes, int rem, uint64_t* out, int fide) {
-    if (nodes.n == 0) return 0;
-    if (!(rem > 3 || (rem >= 2 && nodes.n < 131072))) return perft_leaf(st, nodes, rem, out, fide);
-    int64_t cap = PERFT_LEVEL_CAP;
-    if (const char* e = getenv("GC_PERFT_LEVEL_CAP")) cap = atoll(e) > 0 ? atoll(e) : cap;
-    const int n = nodes.n;
-    int64_t *cnt = nullptr, *offs = nullptr;
-    u64* cb = nullptr;
-    u32* cm = nullptr;
-    uint64_t* cval = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    int64_t held = 0;  // children the buffers below can hold
-    std::string err;
-    auto release = [&]() {
-        (void)hipStreamSynchronize(st);  // nothing in flight may still use the buffers
-        void* ps[] = {cnt, offs, cb, cm, cval, tmp};
-        for (void* q : ps) (void)hipFree(q);
-        cb = nullptr; cm = nullptr; cval = nullptr;
-    };
-    if (dalloc(&cnt, n) || dalloc(&offs, n)) { release(); return -1; }
-    if (fide) k_fcount_children<<<grid_for(n), BLOCK, 0, st>>>(nodes, cnt);
-    else k_count_children<int64_t><<<grid_for(n), BLOCK, 0, st>>>(nodes, cnt);
-    hipError_t he = hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cnt, offs, n, st);
-    if (he != hipSuccess || dalloc((char**)&tmp, tmp_bytes ? tmp_bytes : 1)) {
-        release();
-        return he != hipSuccess ? fail(std::string("perft scan: ") + hipGetErrorString(he)) : -1;
-    }
-    int chunk = n;
-    for (int a = 0; a < n;) {
-        const int c = n - a < chunk ? n - a : chunk;
-        size_t tb = tmp_bytes;
-        int64_t lo = 0, lc = 0;
-        he = hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt + a, offs, c, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(&lo, offs + c - 1, 8, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(&lc, cnt + a + c - 1, 8, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) { err = std::string("perft scan: ") + hipGetErrorString(he); break; }
-        const int64_t total = lo + lc;
-        if (total > cap && c > 1) { chunk = (c + 1) / 2; continue; }  // halve the chunk and rescan
-        if (total >= ((int64_t)1 << 31)) { err = "perft: one node has too many children"; break; }
-        if (total > held) {  // (re)allocate the child buffers for this chunk
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(cb); (void)hipFree(cm); (void)hipFree(cval);
-            cb = nullptr; cm = nullptr; cval = nullptr;
-            held = 0;
-            if (dalloc(&cb, (size_t)NBB * total) || dalloc(&cm, total) || dalloc(&cval, total)) { err = g_err; break; }
-            held = total;
-        }
-        if (total > 0) {
-            SoA ch{cb, cm, (int)total};
-            if (fide) k_fexpand_range<<<grid_for(c), BLOCK, 0, st>>>(nodes, a, c, offs, ch);
-            else k_expand_range<int64_t><<<grid_for(c), BLOCK, 0, st>>>(nodes, a, c, offs, ch);
-            he = hipGetLastError();
-            if (he != hipSuccess) { err = std::string("perft expand: ") + hipGetErrorString(he); break; }
-            if (perft_nodes(st, ch, rem - 1, cval, fide)) { err = g_err; break; }
-        }
-        k_sum_children<int64_t><<<grid_for(c), BLOCK, 0, st>>>(offs, cnt + a, cval, c, out + a);
-        he = hipGetLastError();
-        if (he != hipSuccess) { err = std::string("perft sum: ") + hipGetErrorString(he); break; }
-        a += c;
-    }
-    release();
-    return err.empty() ? 0 : fail(err);
-}
-
-// perft over n roots (side to move = meta[0])
-static int perft_device(hipStream_t st, SoA roots, int depth, uint64_t* d_out, int fide) {
-    if (perft_nodes(st, roots, depth, d_out, fide)) return -1;
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) return fail(std::string("perft kernels: ") + hipGetErrorString(he));
-    return 0;
-}
-
-extern "C" int gc_perft_path_counts(uint64_t* out4) {
-    if (!out4) return fail("null argument");
-    for (int k = 0; k < 4; k++) out4[k] = g_perft_path[k].load();
-    return 0;
-}
-
-extern "C" int gc_perft_leaf_stats(uint64_t* launches, uint64_t* subtrees, double* kernel_ms) {
-    if (!launches || !subtrees || !kernel_ms) return fail("null argument");
-    std::lock_guard<std::mutex> lk(g_leaf_mu);
-    *launches = g_leaf_launches;
-    *subtrees = g_leaf_subtrees;
-    *kernel_ms = g_leaf_ms;
-    return 0;
-}
-
-extern "C" int gc_perft_dedup_stats(uint64_t* records, uint64_t* counted) {
-    if (!records || !counted) return fail("null argument");
-    std::lock_guard<std::mutex> lk(g_leaf_mu);
-    *records = g_leaf_records;
-    *counted = g_leaf_subtrees;
-    return 0;
-}
-
-extern "C" int gc_engine_perft(gc_engine* e, int n, const int8_t* boards, const uint8_t* meta, int depth,
-                               uint64_t* nodes) {
-    if (!e || !nodes) return fail("null argument");
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (depth < 0 || depth > PERFT_MAXD) return fail("depth must be in [0, 8]");
-    if (devsrv_quiesce(e->device) || engine_reserve(e, n, 1)) return -1;
-    EngineLayout o;
-    if (engine_upload(e, n, boards, meta, nullptr, o)) return -1;
-    if (perft_device(e->stream, SoA{e->bb, e->meta, n}, depth, e->u64o, e->rules)) return -1;
-    HIPCHK(hipMemcpyAsync(nodes, e->u64o, (size_t)8 * n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// ----------------------------------------------------------------------------- env API
-#define GC_MAX_SUBSTREAMS 8
-#ifndef GC_DEFAULT_STREAMS
-#define GC_DEFAULT_STREAMS 2  // measured: 1 stream 10.2 us per ply, 2 streams 9.8, 3 10.6, 4 17 (graph-captured 11.4)
-#endif
-struct gc_env {
-    int device = 0, n = 0;
-    uint64_t seed = 0;
-    hipStream_t stream = nullptr;
-    EnvDev d{};
-    u64* bb = nullptr; u32* meta = nullptr;
-    int8_t* mbox = nullptr; uint8_t* m8 = nullptr; uint8_t* mask = nullptr;
-    uint16_t* list = nullptr; int list_cap = 0; int32_t* counts = nullptr; u64* lmask = nullptr;
-    uint64_t* stats = nullptr;
-    hipEvent_t ev[8] = {};
-    bool policy_ready = false;  // act[] holds policy picks for the current states
-    int rules = 0;              // 0 reference, 1 FIDE (gc_fide.h)
-    int8_t* ep = nullptr;       // FIDE ingest: en-passant files
-    ApiOut* api_out = nullptr;  // the paired API step's output pointers (device copy of api_host)
-    ApiOut api_host{};
-    uint16_t* reset_acts = nullptr;
-    EnvDev::InitCache* icd = nullptr;  // device copy of d.ic (the paired kernels read it from HBM)
-    EnvDev::InitCache* icd_f = nullptr;  // the same for the FIDE reset position (gc_env_set_rules)
-    uint16_t* racts_f = nullptr;
-    OpenCache* open_cache = nullptr;     // a BLACK agent's openings (k_init_open_cache, gc_env_set_opponent)
-    uint16_t* open_acts = nullptr;
-    EnvDev::InitCache ic_f = {};
-    uint8_t* slab = nullptr;  // per-board fields (Slab): bb, meta, hgen, draw, nsteps, reward, act, done, reason
-    // Board-range streams of gc_env_step_random (gc_env_set_streams): ply p+1 of one range
-    // depends only on ply p of the same range, so the ranges' launches interleave and the
-    // launch ramp / tail of one range's ply overlaps another range's waves.
-    int n_sub = 1;
-    hipStream_t sub[GC_MAX_SUBSTREAMS] = {};
-    hipEvent_t sub_ev[GC_MAX_SUBSTREAMS] = {};
-    hipEvent_t fork_ev = nullptr;
-    // the spill table of a BLACK agent's windows (gc_env.h; SpillTab): its slot counters are
-    // copied to pinned host memory after every stepping call and checked before the next one
-    int sp_bits = 0;
-    u32* sp_ctr_h = nullptr;  // pinned: {slots claimed, failed}
-    hipEvent_t sp_ev = nullptr;
-    int sp_pending = 0;       // stepping calls since the last counter copy was read
-    bool sp_failed = false;   // an insert failed: every stepping call fails until the windows are cleared
-    gc_single_record* srec = nullptr;  // gc_env_single_call's host-mapped record
-    gc_single_record* srec_d = nullptr;  // its device address
-    // the quad rollout's completion word (EnvDev::InitCache::DoneWord): its host-mapped copy,
-    // the launches issued so far, and the count the last gc_env_rollout_device call waits for
-    // (0: the last call's work was not a quad launch -- gc_env_wait_rollout syncs the stream)
-    u32* done_host = nullptr;
-    u32* done_dev = nullptr;  // {ctr, seq}
-    u32 done_issued = 0;
-    u32 done_expect = 0;
-    // the single-board server (k_single_server): its mailbox (host-mapped), stream, the launch
-    // running (0: none), the last request served
-    SrvBox* srv = nullptr;
-    SrvBox* srv_d = nullptr;
-    hipStream_t srv_stream = nullptr;
-    u32 srv_launch = 0, srv_next_launch = 0, srv_seq = 0;
-    int srv_board = -1;
-};
-
-static int srv_stop(gc_env* e);  // (the single-board server, below)
-// before any launch on the env's device: no resident server (its own or another owner's) holds a queue
-#define SRV_QUIESCE(e) do { if (devsrv_quiesce((e)->device)) return -1; } while (0)
-
-static void env_free(gc_env* e) {
-    void* ps[] = {e->api_out, e->reset_acts, e->icd, e->icd_f, e->racts_f, e->open_cache, e->open_acts, e->ep, e->slab, e->d.htab, e->mbox, e->m8, e->mask,
-                  e->list, e->counts, e->lmask, e->stats};
-    for (void* p : ps) if (p) (void)hipFree(p);
-    for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
-    for (int j = 0; j < GC_MAX_SUBSTREAMS; j++) {
-        if (e->sub_ev[j]) (void)hipEventDestroy(e->sub_ev[j]);
-        if (e->sub[j]) (void)hipStreamDestroy(e->sub[j]);
-    }
-    if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
-    if (e->d.ic.spill.ent) (void)hipFree(e->d.ic.spill.ent);
-    if (e->d.ic.spill.ctr) (void)hipFree(e->d.ic.spill.ctr);
-    if (e->sp_ctr_h) (void)hipHostFree(e->sp_ctr_h);
-    if (e->sp_ev) (void)hipEventDestroy(e->sp_ev);
-    if (e->srec) (void)hipHostFree(e->srec);
-    if (e->done_host) (void)hipHostFree(e->done_host);
-    if (e->srv) (void)hipHostFree(e->srv);
-    if (e->srv_stream) (void)hipStreamDestroy(e->srv_stream);
-    if (e->done_dev) (void)hipFree(e->done_dev);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-}
-
-// ----------------------------------------------------------------------------- spill table
-// A BLACK agent's games have no move cap (chess_v2.py:291-292), so its 3-fold window is
-// unbounded (saved_boards, chess_v2.py:192, 404-407).  Boards of a window past its per-board
-// table's hist_cap go to the env's spill table (gc_env.h spill_find / spill_insert).  The
-// host keeps the table's load under 1/4: after each stepping call the slot counters are
-// copied to pinned memory; before the next call (or, when the copy has not landed, after at
-// most SPILL_CHECK_LAG calls, synchronously) they are read, and a table past 1/4 is rehashed
-// -- dead entries dropped, doubled when the live ones pass 1/8.  A failed insert (no free
-// slot within SPILL_PROBES) sets a sticky flag: the next call reports it as an error, and so
-// does every stepping call after it until every window is cleared (gc_env_reset of all
-// boards, gc_env_set_states, gc_env_load), which starts a fresh table.
-// Multi-step calls (gc_env_step_random, the fused rollouts) cannot wait for the next call:
-// a launch's window generations are published only when it ends, so no entry it makes dead
-// is reclaimed within it.  They run in chunks (spill_chunk): before each, the counters and a
-// census of the windows within SPILL_PER_STEP x SPILL_CHUNK boards of the per-board cap are
-// read, and the chunk is sized so that even if every such window spilled at every step the
-// slots in use stay under half the table (rehashed / doubled first when that leaves fewer
-// than SPILL_CHUNK_MIN steps).
-#define SPILL_CHECK_LAG 4
-#define SPILL_CHUNK 128      // steps per launch of a spill-enabled multi-step call, at most
-#define SPILL_CHUNK_MIN 16   // below this many steps of room the table is rehashed / doubled first
-#define SPILL_PER_STEP 2     // window boards one step adds: the agent's and the opponent's pre-move boards
-#define SPILL_BITS_MAX 30    // 2^30 entries = 64 GiB
-
-// boards whose window is within SPILL_PER_STEP x SPILL_CHUNK boards of the per-board cap
-__global__ void k_spill_census(const u32* __restrict__ meta, int n, u32 thresh, u32* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool near = i < n && hl_of(meta[i]) >= thresh;
-    const unsigned long long b = __ballot(near);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(out, (u32)__popcll(b));
-}
-
-__global__ void k_spill_rehash(const u64* __restrict__ old, u32 old_mask, SpillTab nt, const u32* __restrict__ hgen) {
-    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot > old_mask) return;
-    const u64* e = old + slot * 8;
-    const u64 hdr = e[0];
-    const u32 o1 = sp_owner1(hdr);
-    if (o1 == 0 || sp_gen(hdr) != hgen[o1 - 1]) return;  // empty or dead
-    Pos b = {e[1], e[2], e[3], e[4], e[5], e[6], e[7], 0};
-    DevHist h{nullptr, const_cast<u32*>(hgen), sp_gen(hdr), (int)(o1 - 1), HTAB_BITS_UNCAPPED};
-    h.sp = nt;
-    u32 t = sp_home(board_key(b), o1 - 1, nt.mask);
-    for (int probe = 0; probe < SPILL_PROBES; probe++, t = (t + 1) & nt.mask) {
-        u64 z = 0;
-        if (h.sp_cas(t, z, hdr)) {
-            h.sp_put(t, b);
-            h.sp_claimed();
-            return;
-        }
-    }
-    h.sp_fail();
-}
-
-static int spill_bits_max() {
-    const char* v = getenv("GC_SPILL_BITS_MAX");  // tests: cap the growth to force a failed insert
-    return v && atoi(v) >= 6 && atoi(v) < SPILL_BITS_MAX ? atoi(v) : SPILL_BITS_MAX;
-}
-
-static int spill_bits_for(int n) {
-    int b = 14;
-    while (b < 22 && (1 << (b - 4)) < n) b++;  // 2^20 entries (64 MiB) at 65 536 boards
-    const char* v = getenv("GC_SPILL_BITS");   // tests: start small to drive the rehash / growth path
-    if (v && atoi(v) >= 6 && atoi(v) <= 30) b = atoi(v);
-    return b;
-}
-
-// publish e->d.ic.spill to the device copy the paired kernels read
-static int spill_publish(gc_env* e) {
-    HIPCHK(hipMemcpyAsync(&e->icd->spill, &e->d.ic.spill, sizeof(SpillTab), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-static int spill_alloc(gc_env* e, int bits) {
-    SpillTab t = {nullptr, nullptr, (1u << bits) - 1};
-    if (dalloc(&t.ent, (size_t)8 << bits)) return -1;
-    if (dalloc(&t.ctr, 4)) { (void)hipFree(t.ent); return -1; }
-    hipError_t he = hipMemsetAsync(t.ent, 0, (size_t)64 << bits, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(t.ctr, 0, 16, e->stream);
-    if (he == hipSuccess && !e->sp_ctr_h) he = hipHostMalloc(&e->sp_ctr_h, 16, hipHostMallocDefault);
-    if (he == hipSuccess && !e->sp_ev) he = hipEventCreateWithFlags(&e->sp_ev, hipEventDisableTiming);
-    if (he != hipSuccess) { (void)hipFree(t.ent); (void)hipFree(t.ctr); return fail(std::string("spill table: ") + hipGetErrorString(he)); }
-    if (e->d.ic.spill.ent) (void)hipFree(e->d.ic.spill.ent);
-    if (e->d.ic.spill.ctr) (void)hipFree(e->d.ic.spill.ctr);
-    e->d.ic.spill = t;
-    e->sp_bits = bits;
-    e->sp_pending = 0;
-    e->sp_failed = false;
-    e->sp_ctr_h[0] = e->sp_ctr_h[1] = e->sp_ctr_h[2] = 0;
-    return spill_publish(e);
-}
-
-static void spill_drop(gc_env* e) {
-    if (e->d.ic.spill.ent) (void)hipFree(e->d.ic.spill.ent);
-    if (e->d.ic.spill.ctr) (void)hipFree(e->d.ic.spill.ctr);
-    e->d.ic.spill = SpillTab{nullptr, nullptr, 0};
-    e->sp_bits = 0;
-    e->sp_pending = 0;
-}
-
-// rehash the live entries into a table of 2^bits slots (the stream is idle)
-static int spill_rehash(gc_env* e, int bits) {
-    const SpillTab old = e->d.ic.spill;
-    SpillTab t = {nullptr, nullptr, (1u << bits) - 1};
-    if (dalloc(&t.ent, (size_t)8 << bits)) return -1;
-    if (dalloc(&t.ctr, 4)) { (void)hipFree(t.ent); return -1; }
-    u32 c[2] = {0, 0};
-    hipError_t he = hipMemsetAsync(t.ent, 0, (size_t)64 << bits, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(t.ctr, 0, 16, e->stream);
-    if (he == hipSuccess) {
-        const size_t slots = (size_t)old.mask + 1;
-        k_spill_rehash<<<(unsigned)((slots + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(old.ent, old.mask, t, e->d.hgen);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(c, t.ctr, 8, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess || c[1]) {
-        (void)hipFree(t.ent); (void)hipFree(t.ctr);
-        return fail(he != hipSuccess ? std::string("spill rehash: ") + hipGetErrorString(he)
-                                     : std::string("spill rehash: no free slot (table of 2^") + std::to_string(bits) + ")");
-    }
-    (void)hipFree(old.ent);
-    (void)hipFree(old.ctr);
-    e->d.ic.spill = t;
-    e->sp_bits = bits;
-    e->sp_pending = 0;
-    e->sp_ctr_h[0] = c[0];
-    e->sp_ctr_h[1] = 0;
-    return spill_publish(e);
-}
-
-static int spill_failed(gc_env* e) {
-    e->sp_failed = true;
-    return fail("repetition spill table: an insert found no free slot (a window outgrew 2^" + std::to_string(e->sp_bits) +
-                " shared entries); results since then are invalid until every window is cleared (gc_env_reset of all "
-                "boards, gc_env_set_states or gc_env_load)");
-}
-
-// every window was cleared (the stream is idle): a failed table starts afresh
-static int spill_windows_cleared(gc_env* e) {
-    if (!e->d.ic.spill.ent || !e->sp_failed) return 0;
-    return spill_alloc(e, e->sp_bits);
-}
-
-// before a stepping call: the counters of the last copy that landed
-static int spill_before(gc_env* e) {
-    if (!e->d.ic.spill.ent) return 0;
-    if (e->sp_failed) return spill_failed(e);
-    if (!e->sp_pending) return 0;
-    if (e->sp_pending >= SPILL_CHECK_LAG) HIPCHK(hipEventSynchronize(e->sp_ev));
-    else if (hipEventQuery(e->sp_ev) != hipSuccess) return 0;  // not landed yet: check next call
-    e->sp_pending = 0;
-    const u32 used = e->sp_ctr_h[0], failed = e->sp_ctr_h[1];
-    if (failed) return spill_failed(e);
-    const u32 cap = 1u << e->sp_bits;
-    if (used > cap / 4) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (spill_rehash(e, e->sp_bits)) return -1;  // drops the dead entries
-        if (e->sp_ctr_h[0] > cap / 8 && e->sp_bits < spill_bits_max() && spill_rehash(e, e->sp_bits + 1)) return -1;
-    }
-    return 0;
-}
-
-// the steps the next launch of a multi-step call may take (<= want; synchronous): see above
-static int spill_chunk(gc_env* e, int want) {
-    if (!e->d.ic.spill.ent || want <= 0) return want;
-    if (e->sp_failed) return spill_failed(e);
-    const u32 thresh = (u32)(hist_cap(HTAB_BITS_UNCAPPED) - SPILL_PER_STEP * SPILL_CHUNK);
-    bool rehashed = false;
-    for (;;) {
-        u32* ctr = e->d.ic.spill.ctr;
-        HIPCHK(hipMemsetAsync(ctr + 2, 0, 4, e->stream));
-        k_spill_census<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st.meta, e->n, thresh, ctr + 2);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->sp_ctr_h, ctr, 12, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->sp_pending = 0;
-        const u32 used = e->sp_ctr_h[0], near = e->sp_ctr_h[2];
-        if (e->sp_ctr_h[1]) return spill_failed(e);
-        const uint64_t half = (uint64_t)1 << (e->sp_bits - 1);
-        const uint64_t room = half > used ? half - used : 0;
-        uint64_t steps = near ? room / ((uint64_t)SPILL_PER_STEP * near) : (uint64_t)SPILL_CHUNK;
-        if (steps > SPILL_CHUNK) steps = SPILL_CHUNK;
-        if (steps > (uint64_t)want) steps = (uint64_t)want;
-        const uint64_t enough = want < SPILL_CHUNK_MIN ? (uint64_t)want : (uint64_t)SPILL_CHUNK_MIN;
-        if (steps >= enough) return (int)steps;
-        if (e->sp_bits >= spill_bits_max()) {
-            if (steps >= 1 || rehashed) return steps >= 1 ? (int)steps : 1;  // (a failed insert would be reported)
-            if (spill_rehash(e, e->sp_bits)) return -1;  // the dead entries, at least
-            rehashed = true;
-            continue;
-        }
-        // too little room: drop the dead entries first, then double
-        if (spill_rehash(e, rehashed ? e->sp_bits + 1 : e->sp_bits)) return -1;
-        rehashed = true;
-    }
-}
-
-// after a stepping call: copy the counters (asynchronously) for the next check
-static int spill_after(gc_env* e) {
-    if (!e->d.ic.spill.ent) return 0;
-    HIPCHK(hipMemcpyAsync(e->sp_ctr_h, e->d.ic.spill.ctr, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipEventRecord(e->sp_ev, e->stream));
-    e->sp_pending++;
-    return 0;
-}
-
-// the spill table's state (synchronous): log2 slots (0: none), slots in use (live + dead),
-// live entries
-__global__ void k_spill_live(const u64* __restrict__ ent, u32 mask, const u32* __restrict__ hgen,
-                             unsigned long long* __restrict__ live) {
-    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot > mask) return;
-    const u64 hdr = ent[slot * 8];
-    const u32 o1 = sp_owner1(hdr);
-    if (o1 != 0 && sp_gen(hdr) == hgen[o1 - 1]) atomicAdd(live, 1ull);
-}
-extern "C" int gc_env_spill_info(gc_env* e, int* bits, uint64_t* used, uint64_t* live) {
-    if (!e || !bits || !used || !live) return fail("null argument");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    *bits = e->sp_bits;
-    *used = *live = 0;
-    const SpillTab& sp = e->d.ic.spill;
-    if (!sp.ent) return 0;
-    unsigned long long* d = nullptr;
-    if (dalloc(&d, 1)) return -1;
-    u32 c[2] = {0, 0};
-    unsigned long long lv = 0;
-    hipError_t he = hipMemsetAsync(d, 0, 8, e->stream);
-    if (he == hipSuccess) {
-        const size_t slots = (size_t)sp.mask + 1;
-        k_spill_live<<<(unsigned)((slots + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(sp.ent, sp.mask, e->d.hgen, d);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(&lv, d, 8, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(c, sp.ctr, 8, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    (void)hipFree(d);
-    if (he != hipSuccess) return fail(std::string("spill info: ") + hipGetErrorString(he));
-    *used = c[0];
-    *live = lv;
-    if (c[1]) return fail("repetition spill table: an insert found no free slot");
-    return 0;
-}
-
-// The repetition tables for move-capped games (HTAB_BITS) or for a BLACK agent's uncapped
-// ones (HTAB_BITS_UNCAPPED + the spill table); the stream is idle, the windows are cleared.
-static int set_window_kind(gc_env* e, bool uncapped) {
-    const int bits = uncapped ? HTAB_BITS_UNCAPPED : HTAB_BITS;
-    if (bits != e->d.hbits) {
-        size_t nb64 = ((size_t)e->n + 63) / 64 * 64;
-        u64* t = nullptr;
-        if (dalloc(&t, ((size_t)8 << bits) * nb64)) return -1;
-        HIPCHK(hipMemsetAsync(t, 0, ((size_t)64 << bits) * nb64, e->stream));
-        (void)hipFree(e->d.htab);
-        e->d.htab = t;
-        e->d.hbits = bits;
-    }
-    if (uncapped && !e->d.ic.spill.ent) {  // a BLACK agent's windows may outgrow the table
-        if (spill_alloc(e, spill_bits_for(e->n))) return -1;
-    } else if (!uncapped && e->d.ic.spill.ent) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        spill_drop(e);
-        if (spill_publish(e)) return -1;
-    }
-    return 0;
-}
-
-// kernel dispatch on the env's opponent mode (a kernel-argument-uniform choice made once per
-// launch on the host, so the opponent="none" kernels carry no opponent code)
-static void launch_reset(gc_env* e, const uint8_t* mask, int select) {
-    if (e->rules && e->d.opp) k_fenv_reset<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, mask, select);
-    else if (e->rules) k_fenv_reset<false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, mask, select);
-    else if (e->d.opp) k_env_reset<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, mask, select);
-    else k_env_reset<false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, mask, select);
-}
-template <bool POLICY>
-static void launch_step(gc_env* e) {
-    if (e->rules && e->d.opp) k_fenv_step<POLICY, true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-    else if (e->rules) k_fenv_step<POLICY, false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-    else if (e->d.opp) k_env_step<POLICY, true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-    else k_env_step<POLICY, false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-}
-
-// the reset position's cache of the env's rules (reference or FIDE) for the paired kernels
-struct ResetInfo {
-    const EnvDev::InitCache* icd;
-    const uint16_t* racts;
-    u32 rinfo;  // table << 16 | total
-};
-static ResetInfo reset_info(const gc_env* e) {
-    const EnvDev::InitCache& ic = e->rules ? e->ic_f : e->d.ic;
-    return ResetInfo{e->rules ? e->icd_f : e->icd, e->rules ? e->racts_f : e->d.reset_acts,
-                     (ic.table ? 1u << 16 : 0u) | (u32)(ic.total & 0xFFFF)};
-}
-
-// The paired kernels serve opponent "none" (both rules) and the random opponent when the
-// start position's picks come from its table and, for a BLACK agent, no opening can end in
-// both kings checked (pair_step_vs); otherwise the one-wave kernels run.
-// the reset picks of the self-play policy (reference rules): the move-set order table
-static const uint16_t* sw_table(const ResetInfo& r) {
-    return r.racts ? r.racts + RESET_ACTS_MAX : r.racts;
-}
-static bool pair_ok(const gc_env* e) {
-    if (!e->d.opp) return true;
-    if (e->rules) return false;  // FIDE with the random opponent: the one-wave kernels (k_fenv_*)
-    const EnvDev::InitCache& ic = e->d.ic;
-    return ic.usable && ic.table && (!e->d.agent_black || ic.open_safe);
-}
-static int pair_opp(const gc_env* e) { return e->d.opp ? (e->d.agent_black ? 2 : 1) : 0; }
-
-// one ply (opponent: one two-ply step) of the paired step kernel over the board blocks
-// [b0, b0 + nb) (64 boards each)
-static void launch_step2(gc_env* e, hipStream_t st, int b0 = 0, int nb = -1) {
-    const EnvDev& d = e->d;
-    const ResetInfo r = reset_info(e);
-    const int per_wg = PAIR_BOARDS * PAIRS_WG;
-    if (nb < 0) nb = (e->n + PAIR_BOARDS - 1) / PAIR_BOARDS;
-    const dim3 grid((nb + PAIRS_WG - 1) / PAIRS_WG), block(2 * per_wg);
-    switch (e->rules ? 3 : pair_opp(e)) {
-        case 3: k_env_step2<true><<<grid, block, 0, st>>>(e->slab, d.n, b0, d.seed, d.htab, r.racts, r.icd, r.rinfo); break;
-        case 0: k_env_step2<false><<<grid, block, 0, st>>>(e->slab, d.n, b0, d.seed, d.htab, sw_table(r), r.icd, r.rinfo); break;
-        case 1: k_env_step2<false, 1><<<grid, block, 0, st>>>(e->slab, d.n, b0, d.seed, d.htab, sw_table(r), r.icd, r.rinfo); break;
-        default: k_env_step2<false, 2><<<grid, block, 0, st>>>(e->slab, d.n, b0, d.seed, d.htab, sw_table(r), r.icd, r.rinfo); break;
-    }
-}
-
-extern "C" int gc_env_create(int device, int n_boards, uint64_t seed, const int8_t* initial_board, gc_env** out) {
-    if (!out) return fail("null out pointer");
-    if (n_boards <= 0) return fail("n_boards must be > 0");
-    int nd = 0;
-    HIPCHK(hipGetDeviceCount(&nd));
-    if (device < 0 || device >= nd) return fail("device index out of range");
-    static const int8_t DEF[64] = {-3, -5, -4, -2, -1, -4, -5, -3, -6, -6, -6, -6, -6, -6, -6, -6,
-                                   0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,
-                                   0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,
-                                   6,  6,  6,  6,  6,  6,  6,  6,  3,  5,  4,  2,  1,  4,  5,  3};
-    const int8_t* ib = initial_board ? initial_board : DEF;
-    if (check_boards(1, ib)) return -1;
-    gc_env* e = new gc_env();
-    e->device = device;
-    e->n = n_boards;
-    e->seed = seed;
-    int n = n_boards;
-    size_t nb64 = ((size_t)n + 63) / 64 * 64;  // the window tables come in blocks of 64 boards
-    hipError_t he = hipSetDevice(device);
-    if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (he != hipSuccess) { env_free(e); delete e; return fail(std::string("stream: ") + hipGetErrorString(he)); }
-    if (dalloc(&e->slab, Slab::BYTES_PER_BOARD * (size_t)n) ||
-        dalloc(&e->d.htab, (size_t)HTAB * 8 * nb64) || dalloc(&e->mbox, (size_t)64 * n) ||
-        dalloc(&e->m8, (size_t)8 * n) || dalloc(&e->mask, n) || dalloc(&e->counts, n) || dalloc(&e->stats, (size_t)8 * n + 8) /* [n][8] + the 8 sums */) {
-        std::string m = g_err;
-        env_free(e); delete e;
-        return fail(m);
-    }
-    {
-        uint8_t* sl = e->slab;
-        size_t nz = (size_t)n;
-        e->bb = reinterpret_cast<u64*>(sl);
-        e->meta = reinterpret_cast<u32*>(sl + Slab::meta(nz));
-        e->d.hgen = reinterpret_cast<u32*>(sl + Slab::hgen(nz));
-        e->d.draw = reinterpret_cast<u32*>(sl + Slab::draw(nz));
-        e->d.nsteps = reinterpret_cast<u32*>(sl + Slab::nsteps(nz));
-        e->d.reward = reinterpret_cast<int32_t*>(sl + Slab::reward(nz));
-        e->d.act = reinterpret_cast<uint16_t*>(sl + Slab::act(nz));
-        e->d.done = sl + Slab::done(nz);
-        e->d.reason = sl + Slab::reason(nz);
-    }
-    // initial board bitboards (pure data conversion of the caller's input; no engine work)
-    Pos ip = from_mailbox(ib, 0);
-    u64 ibb[NBB] = {ip.k, ip.q, ip.r, ip.b, ip.n, ip.p, ip.w};
-    for (int j = 0; j < NBB; j++) e->d.init[j] = ibb[j];
-    he = hipSuccess;
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.draw, 0, (size_t)4 * n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.htab, 0, (size_t)64 * HTAB * nb64, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.hgen, 0, (size_t)4 * n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.nsteps, 0, (size_t)4 * n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.reward, 0, (size_t)4 * n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.done, 0, (size_t)n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->d.reason, 0, (size_t)n, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(e->stats, 0, (size_t)64 * n, e->stream);
-    for (auto& v : e->ev) if (he == hipSuccess) he = hipEventCreate(&v);
-    if (he != hipSuccess) { env_free(e); delete e; return fail(std::string("env init: ") + hipGetErrorString(he)); }
-    e->d.st = SoA{e->bb, e->meta, n};
-    e->d.seed = seed;
-    e->d.n = n;
-    e->d.opp = 0;
-    e->d.agent_black = 0;
-    e->d.hbits = HTAB_BITS;
-    {  // the start position's move set, shared by every reset (EnvDev::ic)
-        EnvDev::InitCache* dic = nullptr;
-        uint16_t* dacts = nullptr;
-        if (dalloc(&dic, 1) || dalloc(&dacts, 2 * RESET_ACTS_MAX)) {
-            std::string m = g_err; (void)hipFree(dic); env_free(e); delete e; return fail(m);
-        }
-        e->reset_acts = dacts;
-        e->d.reset_acts = dacts;
-        e->icd = dic;
-        k_init_cache<<<1, BLOCK, 0, e->stream>>>(e->d, dic, dacts);
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpyAsync(&e->d.ic, dic, sizeof(EnvDev::InitCache), hipMemcpyDeviceToHost, e->stream);
-        if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-        if (he != hipSuccess) { env_free(e); delete e; return fail(std::string("init cache: ") + hipGetErrorString(he)); }
-        // the completion word of the quad rollout (host-mapped, fine-grained)
-        u32* hw = nullptr;
-        he = hipHostMalloc(&hw, 4, hipHostMallocMapped | hipHostMallocCoherent);
-        if (he == hipSuccess) { e->done_host = hw; *hw = 0; he = hipMalloc(&e->done_dev, 8); }
-        if (he == hipSuccess) he = hipMemsetAsync(e->done_dev, 0, 8, e->stream);
-        u32* hwd = nullptr;
-        if (he == hipSuccess) he = hipHostGetDevicePointer((void**)&hwd, hw, 0);
-        if (he == hipSuccess) {
-            e->d.ic.done = EnvDev::InitCache::DoneWord{e->done_dev, e->done_dev + 1, hwd};
-            he = hipMemcpyAsync(&dic->done, &e->d.ic.done, sizeof(e->d.ic.done), hipMemcpyHostToDevice, e->stream);
-        }
-        if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-        if (he != hipSuccess) { env_free(e); delete e; return fail(std::string("completion word: ") + hipGetErrorString(he)); }
-    }
-    launch_reset(e, nullptr, 1);
-    he = hipGetLastError();
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess) { env_free(e); delete e; return fail(std::string("reset: ") + hipGetErrorString(he)); }
-    e->policy_ready = true;
-    {
-        const char* sv = getenv("GC_STREAMS");
-        int k = sv ? atoi(sv) : GC_DEFAULT_STREAMS;
-        if (k > 1 && gc_env_set_streams(e, k)) { std::string m = g_err; env_free(e); delete e; return fail(m); }
-    }
-    *out = e;
-    return 0;
-}
-
-// opponent mode (chess_v2.py:133-181): opponent 0 "none", 1 "random" (the device policy
-// answers inside every step); agent_white 0 = player_color BLACK (requires an opponent: the
-// reference's reset calls the opponent policy to open).  Resets every board.
-extern "C" int gc_env_set_opponent(gc_env* e, int opponent, int agent_white) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (opponent != 0 && opponent != 1) return fail("opponent must be 0 (none) or 1 (random)");
-    if (!agent_white && !opponent) return fail("player_color BLACK needs an opponent (chess_v2.py:208-212)");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (set_window_kind(e, !agent_white)) return -1;
-    e->d.opp = opponent;
-    e->d.agent_black = agent_white ? 0 : 1;
-    if (!agent_white && e->d.ic.table && !e->open_cache) {  // the openings of a BLACK agent's resets
-        if (dalloc(&e->open_cache, RESET_ACTS_MAX) || dalloc(&e->open_acts, (size_t)RESET_ACTS_MAX * RESET_ACTS_MAX))
-            return -1;
-        k_init_open_cache<<<(RESET_ACTS_MAX + BLOCK - 1) / BLOCK, BLOCK, 0, e->stream>>>(
-            e->d, e->icd, e->reset_acts + RESET_ACTS_MAX, e->open_cache, e->open_acts);
-        HIPCHK(hipGetLastError());
-        e->d.ic.open = e->open_cache;
-        e->d.ic.open_acts = e->open_acts;
-        HIPCHK(hipMemcpyAsync(&e->icd->open, &e->d.ic.open, sizeof(e->d.ic.open) + sizeof(e->d.ic.open_acts),
-                              hipMemcpyHostToDevice, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    HIPCHK(hipMemsetAsync(e->d.draw, 0, (size_t)4 * e->n, e->stream));  // fresh policy streams
-    launch_reset(e, nullptr, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->policy_ready = true;
-    return 0;
-}
-
-// rules 0: the reference's (default); 1: FIDE (gc_fide.h; with the random opponent on the
-// one-wave kernels).  Resets every board and restarts the policy streams.
-extern "C" int gc_env_set_rules(gc_env* e, int rules) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (rules != 0 && rules != 1) return fail("rules must be 0 (reference) or 1 (fide)");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (rules && !e->icd_f) {  // the FIDE reset position's move set (paired kernels)
-        if (dalloc(&e->icd_f, 1) || dalloc(&e->racts_f, RESET_ACTS_MAX)) return -1;
-        k_finit_cache<<<1, BLOCK, 0, e->stream>>>(e->d, e->icd_f, e->racts_f);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&e->ic_f, e->icd_f, sizeof(EnvDev::InitCache), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    e->rules = rules;
-    HIPCHK(hipMemsetAsync(e->d.draw, 0, (size_t)4 * e->n, e->stream));
-    launch_reset(e, nullptr, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->policy_ready = true;
-    return 0;
-}
-
-extern "C" int gc_env_destroy(gc_env* e) {
-    if (!e) return 0;
-    (void)hipSetDevice(e->device);
-    (void)srv_stop(e);
-    srv_unregister(e);
-    (void)hipStreamSynchronize(e->stream);
-    env_free(e);
-    delete e;
-    return 0;
-}
-
-extern "C" int gc_env_num_boards(gc_env* e) { return e ? e->n : -1; }
-
-extern "C" int gc_env_reset(gc_env* e, const uint8_t* mask) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    if (mask) HIPCHK(hipMemcpyAsync(e->mask, mask, e->n, hipMemcpyHostToDevice, e->stream));
-    launch_reset(e, mask ? e->mask : nullptr, 1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (!mask && spill_windows_cleared(e)) return -1;
-    e->policy_ready = true;
-    return 0;
-}
-
-// ---- single-board env ops (k_single)
-extern "C" int gc_env_single_setup(gc_env* e, int agent_white) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (e->rules) return fail("the single-board env ops follow the reference's rules");
-    if (e->d.opp) return fail("the single-board env ops drive the opponent from the host (opponent 0)");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (set_window_kind(e, !agent_white)) return -1;
-    if (!e->srec) {
-        HIPCHK(hipHostMalloc(&e->srec, sizeof(gc_single_record), hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->srec_d, e->srec, 0));
-    }
-    return 0;
-}
-
-// ---- the single-board server's host side
-static bool srv_enabled() {
-    static const bool off = getenv("GC_SINGLE_SERVER") && atoi(getenv("GC_SINGLE_SERVER")) == 0;
-    return !off;
-}
-// stop the server (if one runs) and wait until it has drained: every other op on this env
-// reads or writes the board's memory through other kernels
-static int srv_stop(gc_env* e) {
-    DevSrv& s = devsrv(e->device);
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    devsrv_release(s, e);
-    if (!e->srv_launch) return 0;
-    SrvBox* b = e->srv;
-    __atomic_store_n(&b->op, (u32)SRV_QUIT, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->req_seq, e->srv_seq + 1, __ATOMIC_RELEASE);  // (never served: QUIT)
-    const hipError_t he = hipStreamSynchronize(e->srv_stream);
-    __atomic_store_n(&b->req_seq, e->srv_seq, __ATOMIC_RELEASE);
-    e->srv_launch = 0;
-    if (he != hipSuccess) return fail(std::string("single-board server: ") + hipGetErrorString(he));
-    return 0;
-}
-// one op through the server (started on demand); the record lands in e->srec
-static int srv_stop_v(void* e) { return srv_stop(static_cast<gc_env*>(e)); }
-static int srv_call(gc_env* e, int board, int op, int action, int flags) {
-    HIPCHK(hipSetDevice(e->device));
-    DevSrv& s = devsrv(e->device);
-    std::lock_guard<std::recursive_mutex> lk(s.mu);
-    if (devsrv_claim(s, e, srv_stop_v)) return -1;
-    if (!e->srv) {
-        HIPCHK(hipHostMalloc(&e->srv, sizeof(SrvBox), hipHostMallocMapped | hipHostMallocCoherent));
-        memset(e->srv, 0, sizeof(SrvBox));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->srv_d, e->srv, 0));
-        HIPCHK(hipStreamCreateWithFlags(&e->srv_stream, hipStreamNonBlocking));
-    }
-    if (e->srv_launch && e->srv_board != board && (srv_stop(e) || devsrv_claim(s, e, srv_stop_v))) return -1;
-    SrvBox* b = e->srv;
-    const u32 seq = e->srv_seq + 1;
-    __atomic_store_n(&b->op, (u32)op, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->action, action, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->flags, (u32)flags, __ATOMIC_RELAXED);
-    __atomic_store_n(&b->req_seq, seq, __ATOMIC_RELEASE);  // last: the device reads the four words at once
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned k = 0;; k++) {
-        if (!e->srv_launch || __atomic_load_n(&b->exited, __ATOMIC_ACQUIRE) == e->srv_launch) {
-            // no server, or it exited (idle) before seeing this request: (re)start it after the
-            // env's own work; it serves every request past done_seq
-            if (e->srv_launch) HIPCHK(hipStreamSynchronize(e->srv_stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            e->srv_launch = ++e->srv_next_launch;
-            e->srv_board = board;
-            srv_register(e, SrvReg{&b->req_seq, &b->op, &b->exited, &e->srv_seq, &e->srv_launch});
-            k_single_server<<<1, 64, 0, e->srv_stream>>>(e->d, board, e->srv_d, e->srec_d, e->srv_seq, e->srv_launch);
-            HIPCHK(hipGetLastError());
-        }
-        if (__atomic_load_n(&b->resp_seq, __ATOMIC_ACQUIRE) == seq) break;
-        if ((k & 1023) == 1023) {  // a faulted server: the stream says so
-            const hipError_t q = hipStreamQuery(e->srv_stream);
-            if (q != hipSuccess && q != hipErrorNotReady) return fail(std::string("single-board server: ") + hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) {
-                (void)srv_stop(e);
-                return fail("single-board server: no answer within 10 s");
-            }
-        }
-    }
-    e->srv_seq = seq;
-    return 0;
-}
-
-// diagnostic: the server's segments of its last op (10 ns ticks): op, list, record copy, idle
-extern "C" int gc_env_single_stamps(gc_env* e, uint32_t* out6) {
-    if (!e || !out6) return fail("null argument");
-    for (int k = 0; k < 6; k++) out6[k] = e->srv ? __atomic_load_n(&e->srv->stamps[k], __ATOMIC_ACQUIRE) : 0u;
-    return 0;
-}
-
-extern "C" int gc_env_single_call(gc_env* e, int board, int op, int action, int flags, const gc_single_record** rec) {
-    if (!e || !rec) return fail("null argument");
-    if (!e->srec) return fail("call gc_env_single_setup first");
-    if (board < 0 || board >= e->n) return fail("board index out of range");
-    if (op < SOP_RESET || op > SOP_SYNC) return fail("op: 0 reset, 1 agent, 2 reply, 3 open, 4 sync (5 set: gc_env_single_set)");
-    if (op != SOP_RESET && op != SOP_SYNC && (action < 0 || action > A_RESIGN))
-        return fail("action out of range [0, 4100]");
-    HIPCHK(hipSetDevice(e->device));
-    if (e->d.ic.spill.ent) {  // a BLACK agent: the spill table's host checks need the stream
-        if (devsrv_quiesce(e->device) || spill_before(e)) return -1;
-    }
-    if (srv_enabled() && !e->d.ic.spill.ent) {
-        if (srv_call(e, board, op, action, flags)) return -1;
-    } else {
-        if (devsrv_quiesce(e->device)) return -1;
-        k_single<<<1, 64, 0, e->stream>>>(e->d, board, op, action, flags, e->srec_d);
-        HIPCHK(hipGetLastError());
-        if (spill_after(e) || gc_env_synchronize(e)) return -1;
-    }
-    e->policy_ready = false;
-    *rec = e->srec;
-    return 0;
-}
-
-// the state setter (chess_v2.py:315-323) of one board: its pieces and the six flags; the side
-// to move, move_count, done and the 3-fold window stay (k_single's SET)
-extern "C" int gc_env_single_set(gc_env* e, int board, const int8_t* board64, const uint8_t* flags6,
-                                 const gc_single_record** rec) {
-    if (!e || !board64 || !flags6 || !rec) return fail("null argument");
-    if (!e->srec) return fail("call gc_env_single_setup first");
-    if (board < 0 || board >= e->n) return fail("board index out of range");
-    for (int k = 0; k < 64; k++)
-        if (board64[k] < -6 || board64[k] > 6) return fail("board: piece ids are -6..6");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));  // the record is the launch's input here
-    memcpy(e->srec->board, board64, 64);
-    for (int k = 0; k < 4; k++) e->srec->rights[k] = flags6[k] ? 1 : 0;
-    for (int k = 0; k < 2; k++) e->srec->checked[k] = flags6[4 + k] ? 1 : 0;
-    if (srv_enabled() && !e->d.ic.spill.ent) {
-        if (srv_call(e, board, SOP_SET, 0, 0)) return -1;
-    } else {
-        if (devsrv_quiesce(e->device)) return -1;
-        k_single<<<1, 64, 0, e->stream>>>(e->d, board, SOP_SET, 0, 0, e->srec_d);
-        HIPCHK(hipGetLastError());
-        if (gc_env_synchronize(e)) return -1;
-    }
-    e->policy_ready = false;
-    *rec = e->srec;
-    return 0;
-}
-
-extern "C" int gc_env_window_boards(gc_env* e, int board, int8_t* boards, uint8_t* counts, int cap, int* n) {
-    if (!e || !n || (cap > 0 && (!boards || !counts))) return fail("null argument");
-    SRV_QUIESCE(e);
-    if (board < 0 || board >= e->n) return fail("board index out of range");
-    HIPCHK(hipSetDevice(e->device));
-    int8_t* db = nullptr;
-    uint8_t* dc = nullptr;
-    int* dn = nullptr;
-    const int c = cap > 0 ? cap : 0;
-    if (dalloc(&db, (size_t)64 * (c ? c : 1)) || dalloc(&dc, c ? c : 1) || dalloc(&dn, 1)) {
-        (void)hipFree(db); (void)hipFree(dc);
-        return -1;
-    }
-    k_window_boards<<<1, 64, 0, e->stream>>>(e->d, board, db, dc, c, dn);
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpyAsync(n, dn, sizeof(int), hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    const int k = *n < c ? *n : c;
-    if (he == hipSuccess && k) he = hipMemcpy(boards, db, (size_t)64 * k, hipMemcpyDeviceToHost);
-    if (he == hipSuccess && k) he = hipMemcpy(counts, dc, (size_t)k, hipMemcpyDeviceToHost);
-    (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dn);
-    if (he != hipSuccess) return fail(std::string("window readout: ") + hipGetErrorString(he));
-    return 0;
-}
-
-extern "C" int gc_env_step(gc_env* e, const uint16_t* actions, int32_t* reward, uint8_t* done, uint8_t* reason) {
-    if (!e || !actions) return fail("null argument");
-    SRV_QUIESCE(e);
-    for (int i = 0; i < e->n; i++)
-        if (actions[i] > A_RESIGN) return fail("action out of range [0, 4100] at index " + std::to_string(i));
-    HIPCHK(hipSetDevice(e->device));
-    if (spill_before(e)) return -1;
-    HIPCHK(hipMemcpyAsync(e->d.act, actions, (size_t)2 * e->n, hipMemcpyHostToDevice, e->stream));
-    launch_step<false>(e);
-    HIPCHK(hipGetLastError());
-    if (spill_after(e)) return -1;
-    e->policy_ready = false;
-    if (reward) HIPCHK(hipMemcpyAsync(reward, e->d.reward, (size_t)4 * e->n, hipMemcpyDeviceToHost, e->stream));
-    if (done) HIPCHK(hipMemcpyAsync(done, e->d.done, e->n, hipMemcpyDeviceToHost, e->stream));
-    if (reason) HIPCHK(hipMemcpyAsync(reason, e->d.reason, e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// step() with device buffers (k_env_step_api4 and its siblings): asynchronous on the env's
-// stream (gc_env_get_stream); every pointer is device memory of n entries (mask: 65 rows of
-// mask_stride words, word f of board i at f * mask_stride + i; obs: n*64 bytes); mask / obs /
-// count / pick may be NULL.  The stride travels with each call: with n a multiple
-// of a large power of two, packed rows n words apart alias on the same HBM channels, so a caller
-// may pad them (gym_chess_amd.env.DeviceIO does); gc_env_step_device is the packed form.
-extern "C" int gc_env_step_device2(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, uint8_t* d_done,
-                                   uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
-                                   uint16_t* d_pick, int flags, int64_t mask_stride) {
-    if (!e || !d_actions || !d_reward || !d_done || !d_reason) return fail("null argument");
-    SRV_QUIESCE(e);
-    if (flags & ~1) return fail("flags: bit 0 = auto-reset");
-    if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
-    HIPCHK(hipSetDevice(e->device));
-    if (spill_before(e)) return -1;
-    const int ar = flags & 1;
-    const size_t ms = mask_stride ? (size_t)mask_stride : (size_t)e->n;  // the mask rows' stride
-    if (e->rules) {  // FIDE: one lane per board
-        if (e->d.opp)
-            k_fenv_step_api<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, d_actions, d_reward, d_done, d_reason,
-                                                                            d_mask, d_obs, d_count, d_pick, ar, ms);
-        else
-            k_fenv_step_api<false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, d_actions, d_reward, d_done, d_reason,
-                                                                             d_mask, d_obs, d_count, d_pick, ar, ms);
-        HIPCHK(hipGetLastError());
-        if (spill_after(e)) return -1;
-        e->policy_ready = d_pick != nullptr;
-        return 0;
-    }
-    if (!e->d.opp && e->d.ic.usable && e->d.ic.table) {
-        const EnvDev& d = e->d;
-        const ResetInfo r = reset_info(e);
-        const int nb = (e->n + PAIR_BOARDS - 1) / PAIR_BOARDS;
-        const ApiOut o = {d_reward, d_done, d_reason, d_mask, d_obs, d_count, d_pick, ms};
-        if (!e->api_out) {
-            if (dalloc(&e->api_out, 1)) return -1;
-            e->api_host = {};
-        }
-        if (memcmp(&o, &e->api_host, sizeof o) != 0) {  // the caller's buffers changed
-            e->api_host = o;
-            HIPCHK(hipMemcpyAsync(e->api_out, &e->api_host, sizeof o, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));  // api_host may change again before a lazy copy ran
-        }
-        // (over two board-range streams, so a range's store tail could overlap the other's
-        // generation: measured 47 vs 21 us per step with the paired kernel, round 3)
-        k_env_step_api4<<<(nb + QUADS_WG - 1) / QUADS_WG, 4 * QUAD_BOARDS * QUADS_WG, 0, e->stream>>>(
-            e->slab, d.seed, d.htab, r.racts, r.icd, d_actions, e->api_out, d.n, r.rinfo | ((u32)ar << 17));
-    } else if (e->d.opp && pair_ok(e)) {  // the random opponent on the paired driver
-        const EnvDev& d = e->d;
-        const ResetInfo r = reset_info(e);
-        const int nb = (e->n + PAIR_BOARDS - 1) / PAIR_BOARDS;
-        const ApiOut o = {d_reward, d_done, d_reason, d_mask, d_obs, d_count, d_pick, ms};
-        if (!e->api_out) {
-            if (dalloc(&e->api_out, 1)) return -1;
-            e->api_host = {};
-        }
-        if (memcmp(&o, &e->api_host, sizeof o) != 0) {
-            e->api_host = o;
-            HIPCHK(hipMemcpyAsync(e->api_out, &e->api_host, sizeof o, hipMemcpyHostToDevice, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-        }
-        const dim3 grid((nb + PAIRS_WG - 1) / PAIRS_WG), block(2 * PAIR_BOARDS * PAIRS_WG);
-        const char* nq = getenv("GC_NO_QUAD_API");  // A/B and tests (read per call): api2_vs
-        const bool no_quad_vs = nq && atoi(nq) != 0;
-        // (a BLACK agent's resets open with the opponent's move: the openings' positions and moves
-        // are cached, k_init_open_cache -- 33.9 vs 41.1 us per launch for the paired kernel,
-        // tools/api_color_probe.py; through the per-piece fallback instead: 46.9)
-        if (!no_quad_vs && d.agent_black && d.ic.open)  // four waves per 64 boards (k_env_step_api4_vs)
-            k_env_step_api4_vs<true><<<(nb + QUADS_WG - 1) / QUADS_WG, 4 * QUAD_BOARDS * QUADS_WG, 0, e->stream>>>(
-                e->slab, d.seed, d.htab, r.racts, r.icd, d_actions, e->api_out, d.n, r.rinfo | ((u32)ar << 17));
-        else if (!no_quad_vs && !d.agent_black)
-            k_env_step_api4_vs<false><<<(nb + QUADS_WG - 1) / QUADS_WG, 4 * QUAD_BOARDS * QUADS_WG, 0, e->stream>>>(
-                e->slab, d.seed, d.htab, r.racts, r.icd, d_actions, e->api_out, d.n, r.rinfo | ((u32)ar << 17));
-        else if (d.agent_black)
-            k_env_step_api2_vs<true><<<grid, block, 0, e->stream>>>(e->slab, d.seed, d.htab, r.racts, r.icd, d_actions,
-                                                                     e->api_out, d.n, r.rinfo | ((u32)ar << 17));
-        else
-            k_env_step_api2_vs<false><<<grid, block, 0, e->stream>>>(e->slab, d.seed, d.htab, r.racts, r.icd, d_actions,
-                                                                      e->api_out, d.n, r.rinfo | ((u32)ar << 17));
-    } else if (e->d.opp)
-        k_env_step_api<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, d_actions, d_reward, d_done, d_reason,
-                                                                      d_mask, d_obs, d_count, d_pick, ar, ms);
-    else
-        k_env_step_api<false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, d_actions, d_reward, d_done, d_reason,
-                                                                       d_mask, d_obs, d_count, d_pick, ar, ms);
-    HIPCHK(hipGetLastError());
-    if (spill_after(e)) return -1;
-    e->policy_ready = d_pick != nullptr;
-    return 0;
-}
-
-extern "C" int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, uint8_t* d_done,
-                                  uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
-                                  uint16_t* d_pick, int flags) {
-    return gc_env_step_device2(e, d_actions, d_reward, d_done, d_reason, d_mask, d_obs, d_count, d_pick, flags, 0);
-}
-
-// Policy head on the device (gc_policy.h): per board an action sampled from softmax(logits / T)
-// over the legal mask that gc_env_step_device2 wrote (or the greedy one), its log-prob and the
-// entropy.  Reads only the mask and the logits at legal actions: either rule set, either
-// opponent mode.  Asynchronous on the env's stream, so a following gc_env_step_device2 that
-// takes d_action as its actions is ordered after it.
-extern "C" int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
-                                    const uint64_t* d_mask, int64_t mask_stride, float temperature,
-                                    uint64_t seed, uint32_t draw, int flags,
-                                    uint16_t* d_action, float* d_logprob, float* d_entropy) {
-    if (!e || !d_logits || !d_mask || !d_action) return fail("null argument");
-    if (dtype < 0 || dtype > 2) return fail("dtype: 0 float32, 1 float16, 2 bfloat16");
-    if (row_stride < 4100) return fail("row stride below the 4100 move actions");
-    if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0");
-    if (flags & ~1) return fail("flags: bit 0 = greedy");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    PolicyArgs a;
-    a.logits = d_logits;
-    a.row_stride = (size_t)row_stride;
-    a.mask = d_mask;
-    a.mask_stride = mask_stride ? (size_t)mask_stride : (size_t)e->n;
-    a.temperature = temperature;
-    a.seed = seed;
-    a.draw = draw;
-    a.greedy = flags & 1;
-    a.action = d_action;
-    a.logprob = d_logprob;
-    a.entropy = d_entropy;
-    a.n = e->n;
-    const dim3 grid((e->n + POL_TILE - 1) / POL_TILE), block(64 * POL_WAVES);
-    if (dtype == 0) k_sample_policy<0><<<grid, block, 0, e->stream>>>(a);
-    else if (dtype == 1) k_sample_policy<1><<<grid, block, 0, e->stream>>>(a);
-    else k_sample_policy<2><<<grid, block, 0, e->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int gc_env_get_stream(gc_env* e, void** stream) {
-    if (!e || !stream) return fail("null argument");
-    *stream = (void*)e->stream;
-    return 0;
-}
-
-// device buffers for callers without their own allocator (tests, bench): hipMalloc /
-// hipFree on the env's device, and copies on its stream
-extern "C" int gc_device_alloc(int device, uint64_t bytes, void** ptr) {
-    if (!ptr) return fail("null argument");
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(ptr, bytes ? bytes : 1));
-    return 0;
-}
-extern "C" int gc_device_free(int device, void* ptr) {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipFree(ptr));
-    return 0;
-}
-extern "C" int gc_env_copy(gc_env* e, void* dst, const void* src, uint64_t bytes, int kind) {
-    if (!e || !dst || !src) return fail("null argument");
-    if (kind < 0 || kind > 3) return fail("kind: 0 h2h, 1 h2d, 2 d2h, 3 d2d");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, (hipMemcpyKind)kind, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// n plies of the paired step kernel after the work already on the env's stream: on the
-// env's stream, or over the board-range streams (forked from it and joined back into it)
-static int issue_plies(gc_env* e, int n) {
-    if (e->n_sub <= 1) {
-        for (int p = 0; p < n; p++) launch_step2(e, e->stream);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    const int blocks = (e->n + PAIR_BOARDS - 1) / PAIR_BOARDS;
-    const int k = e->n_sub < blocks ? e->n_sub : blocks;
-    // a range is a whole number of workgroups (PAIRS_WG blocks each), so no workgroup reaches
-    // into the next range; only the last range is partial, and beyond it every lane is dead
-    const int per = ((blocks + k - 1) / k + PAIRS_WG - 1) / PAIRS_WG * PAIRS_WG;
-    HIPCHK(hipEventRecord(e->fork_ev, e->stream));
-    for (int j = 0; j < k; j++) HIPCHK(hipStreamWaitEvent(e->sub[j], e->fork_ev, 0));
-    for (int p = 0; p < n; p++)
-        for (int j = 0; j < k; j++) {
-            int b0 = j * per, nb = blocks - b0 < per ? blocks - b0 : per;
-            if (nb > 0) launch_step2(e, e->sub[j], b0, nb);
-        }
-    HIPCHK(hipGetLastError());
-    for (int j = 0; j < k; j++) {
-        HIPCHK(hipEventRecord(e->sub_ev[j], e->sub[j]));
-        HIPCHK(hipStreamWaitEvent(e->stream, e->sub_ev[j], 0));
-    }
-    return 0;
-}
-
-// device-resident random self-play: n_plies launches of the one-ply step kernel (no host
-// traffic, no sync).  Outputs of the LAST ply stay in device buffers (gc_env_get_outputs).
-static int step_random(gc_env* e, int n_plies);
-extern "C" int gc_env_step_random(gc_env* e, int n_plies) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (!e->policy_ready) return fail("policy actions stale: call gc_env_reset or gc_env_select_random first");
-    HIPCHK(hipSetDevice(e->device));
-    if (spill_before(e)) return -1;
-    for (int p = 0; p < n_plies;) {  // one chunk unless the env spills (spill_chunk)
-        const int k = spill_chunk(e, n_plies - p);
-        if (k < 0 || step_random(e, k)) return -1;
-        p += k;
-    }
-    return spill_after(e);
-}
-// (a hipGraph of the plies' launches was measured slower: 11.4 vs 9.8 us per ply, round 2)
-static int step_random(gc_env* e, int n_plies) {
-    const bool pair = pair_ok(e);  // the paired kernel (pair_ok: all but rare opponent setups)
-    int p = 0;
-    if (p < n_plies) {
-        if (pair) return issue_plies(e, n_plies - p);
-        for (; p < n_plies; p++) {
-            launch_step<true>(e);
-            HIPCHK(hipGetLastError());
-        }
-    }
-    return 0;
-}
-
-// board-range streams of gc_env_step_random (1 = the env's stream only)
-extern "C" int gc_env_set_streams(gc_env* e, int k) {
-    if (!e) return fail("null env");
-    if (k < 1 || k > GC_MAX_SUBSTREAMS) return fail("streams must be in [1, 8]");
-    HIPCHK(hipSetDevice(e->device));
-    for (int j = 0; j < k; j++) {
-        if (!e->sub[j]) HIPCHK(hipStreamCreateWithFlags(&e->sub[j], hipStreamNonBlocking));
-        if (!e->sub_ev[j]) HIPCHK(hipEventCreateWithFlags(&e->sub_ev[j], hipEventDisableTiming));
-    }
-    if (!e->fork_ev) HIPCHK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
-    e->n_sub = k;
-    return 0;
-}
-
-extern "C" int gc_env_paired(gc_env* e) {
-    if (!e) return fail("null env");
-    return pair_ok(e) ? 1 : 0;
-}
-
-// The quads take a reset board's pick from the start position's table only (Q1 reads it in
-// phase 0, before the ply's outcome is known); a start position without one (> 16 own pieces,
-// or more than RESET_ACTS_MAX moves) runs on the paired kernel, whose pair_ply regenerates the
-// start position's move sets at a reset.
-static bool use_quad(const gc_env* e) {
-    static const bool no_quad = getenv("GC_NO_QUAD") != nullptr;  // A/B: the paired kernel
-    return !no_quad && !e->rules && pair_opp(e) == 0 && e->d.ic.table;
-}
-
-// The occupancy filter (k_env_rollout4<true>, above) costs Q1 ~700 cycles of phase 1 and the
-// ply ~3 % more cycles (tools/pstamp_probe.py); what it buys is half the ply's HBM bytes, and
-// with them the clock a long launch holds under the power limit (r06h stamps: 2.27 vs 2.18 GHz
-// over 1 000 plies).  Same box, always / never, the workgroups taking turns (profiles/r06_v1/
-// ab_summary.txt, run_r06q): K = 20 12.86 / 13.27e9, 100 15.29 / 15.48, 300 15.73 / 15.90, 500
-// 15.79 / 15.91, 700 15.91 / 15.43, 1 000 15.94 / 15.12, 2 000 16.26 / 15.62 -- so it runs for
-// launches of GC_OCC_MIN_PLIES (600, the crossover) plies or more
-static int occ_min_plies() {
-    static const int v = getenv("GC_OCC_MIN_PLIES") ? atoi(getenv("GC_OCC_MIN_PLIES")) : 600;
-    return v;
-}
-
-extern "C" int gc_env_rollout_occ_min_plies(void) { return occ_min_plies(); }
-
-extern "C" int gc_env_rollout_waves(gc_env* e) {
-    if (!e) return fail("null env");
-    return pair_ok(e) ? (use_quad(e) ? 4 : 2) : 1;
-}
-
-extern "C" int gc_env_select_random(gc_env* e) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    if (e->rules) k_fenv_select<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-    else k_select<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d);
-    HIPCHK(hipGetLastError());
-    e->policy_ready = true;
-    return 0;
-}
-
-// n_plies of fused random self-play after the work already on the env's stream (no host
-// sync): ROLLOUT_MAX_PLIES per launch; the per-ply trace (device memory, [n_plies][N] words,
-// trace_word) when d_trace is not NULL; with `stats`, per-board stats accumulate into e->stats.
-static int issue_rollout(gc_env* e, int n_plies, uint64_t* d_trace, bool stats) {
-    uint64_t* const st = stats ? e->stats : nullptr;
-    const bool pair = pair_ok(e);
-    const EnvDev& d = e->d;
-    const ResetInfo r = reset_info(e);
-    const int grid = (e->n + PAIR_BOARDS * PAIRS_WG - 1) / (PAIR_BOARDS * PAIRS_WG), bs = 2 * PAIR_BOARDS * PAIRS_WG;
-    for (int p0 = 0, k = 0; p0 < n_plies; p0 += k) {
-        k = spill_chunk(e, n_plies - p0 < ROLLOUT_MAX_PLIES ? n_plies - p0 : ROLLOUT_MAX_PLIES);
-        if (k < 0) return -1;
-        u64* tr = d_trace ? reinterpret_cast<u64*>(d_trace) + (size_t)p0 * e->n : nullptr;
-        const u32 ri = r.rinfo | ((u32)k << 18);
-        e->done_expect = 0;
-        if (pair && use_quad(e)) {
-            const int qg = (e->n + QUAD_BOARDS * QUADS_WG - 1) / (QUAD_BOARDS * QUADS_WG);
-            if (k >= occ_min_plies())
-                k_env_rollout4<true><<<qg, 4 * QUAD_BOARDS * QUADS_WG, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab,
-                                                                                      sw_table(r), r.icd, ri, st, tr);
-            else
-                k_env_rollout4<false><<<qg, 4 * QUAD_BOARDS * QUADS_WG, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab,
-                                                                                       sw_table(r), r.icd, ri, st, tr);
-            e->done_expect = ++e->done_issued;
-        } else if (pair) {
-            switch (e->rules ? 3 : pair_opp(e)) {
-                case 3: k_env_rollout2<true><<<grid, bs, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab, r.racts, r.icd, ri, st, tr); break;
-                case 0: k_env_rollout2<false><<<grid, bs, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab, sw_table(r), r.icd, ri, st, tr); break;
-                case 1: k_env_rollout2<false, 1><<<grid, bs, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab, sw_table(r), r.icd, ri, st, tr); break;
-                default: k_env_rollout2<false, 2><<<grid, bs, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab, sw_table(r), r.icd, ri, st, tr); break;
-            }
-        } else if (e->rules) {  // FIDE with the random opponent
-            k_fenv_rollout<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, k, tr, st);
-        } else if (e->d.opp) {
-            k_env_rollout<true><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, k, tr, st);
-        } else {
-            k_env_rollout<false><<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d, k, tr, st);
-        }
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(std::string("rollout launch: ") + hipGetErrorString(le));
-    }
-    return 0;
-}
-
-extern "C" int gc_env_rollout(gc_env* e, int n_plies, int16_t* tr_action, int16_t* tr_reward, uint8_t* tr_done,
-                              uint8_t* tr_reason, uint64_t* stats8) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (n_plies < 0) return fail("n_plies must be >= 0");
-    if (!e->policy_ready) return fail("policy actions stale: call gc_env_reset or gc_env_select_random first");
-    HIPCHK(hipSetDevice(e->device));
-    const bool trace = tr_action || tr_reward || tr_done || tr_reason;
-    const size_t cnt = (size_t)n_plies * e->n;
-    u64* dt = nullptr;
-    if (trace && cnt && dalloc(&dt, cnt)) return -1;
-    if (spill_before(e)) { (void)hipFree(dt); return -1; }
-    HIPCHK(hipMemsetAsync(e->stats, 0, (size_t)64 * e->n, e->stream));
-    if (issue_rollout(e, n_plies, dt, true) || spill_after(e)) { (void)hipFree(dt); return -1; }
-    if (trace && cnt) {
-        std::vector<u64> h(cnt);
-        hipError_t ce = hipMemcpyAsync(h.data(), dt, cnt * 8, hipMemcpyDeviceToHost, e->stream);
-        if (ce == hipSuccess) ce = hipStreamSynchronize(e->stream);
-        (void)hipFree(dt);
-        if (ce != hipSuccess) return fail(std::string("rollout trace: ") + hipGetErrorString(ce));
-        for (size_t t = 0; t < cnt; t++) {
-            const u64 w = h[t];
-            if (tr_action) tr_action[t] = (int16_t)(uint16_t)w;
-            if (tr_reward) tr_reward[t] = (int16_t)(uint16_t)(w >> 16);
-            if (tr_done) tr_done[t] = (uint8_t)(w >> 32);
-            if (tr_reason) tr_reason[t] = (uint8_t)(w >> 40);
-        }
-    }
-    if (stats8) {
-        uint64_t* sums = e->stats + (size_t)8 * e->n;
-        HIPCHK(hipMemsetAsync(sums, 0, 64, e->stream));
-        k_sum_stats<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->stats, e->n, reinterpret_cast<unsigned long long*>(sums));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(stats8, sums, 64, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    return 0;
-}
-
-// n_plies env.step() calls of every board under the random self-play policy in one launch
-// (per ROLLOUT_MAX_PLIES), asynchronous on the env's stream; each ply's outputs land in the
-// device trace [n_plies][N] (trace_word) when d_trace is not NULL.  State, windows, counters
-// and the last ply's outputs afterwards are those of n_plies gc_env_step_random plies.
-// ev_begin / ev_end: event slots (gc_env_record_event) recorded on the env's stream right
-// before / after the launches, -1 = none (one C-ABI call brackets the timed work).
-extern "C" int gc_env_rollout_device(gc_env* e, int n_plies, uint64_t* d_trace, int ev_begin, int ev_end) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    if (n_plies < 0) return fail("n_plies must be >= 0");
-    if (ev_begin < -1 || ev_begin >= 8 || ev_end < -1 || ev_end >= 8) return fail("event slots: -1 or 0..7");
-    if (!e->policy_ready) return fail("policy actions stale: call gc_env_reset or gc_env_select_random first");
-    HIPCHK(hipSetDevice(e->device));
-    if (spill_before(e)) return -1;
-    // marker events around the launches (r03 probe: timing the launches by hipExtLaunchKernel's
-    // own start / stop events cost ~8 us more host time per call at K = 20 -- tools/short_probe.py)
-    if (ev_begin >= 0) HIPCHK(hipEventRecord(e->ev[ev_begin], e->stream));
-    if (issue_rollout(e, n_plies, d_trace, false)) return -1;
-    if (ev_end >= 0) HIPCHK(hipEventRecord(e->ev[ev_end], e->stream));
-    return spill_after(e);
-}
-
-extern "C" int gc_env_get_outputs(gc_env* e, int32_t* reward, uint8_t* done, uint8_t* reason, uint16_t* next_action,
-                                  uint32_t* nsteps) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    if (reward) HIPCHK(hipMemcpyAsync(reward, e->d.reward, (size_t)4 * e->n, hipMemcpyDeviceToHost, e->stream));
-    if (done) HIPCHK(hipMemcpyAsync(done, e->d.done, e->n, hipMemcpyDeviceToHost, e->stream));
-    if (reason) HIPCHK(hipMemcpyAsync(reason, e->d.reason, e->n, hipMemcpyDeviceToHost, e->stream));
-    if (next_action) HIPCHK(hipMemcpyAsync(next_action, e->d.act, (size_t)2 * e->n, hipMemcpyDeviceToHost, e->stream));
-    if (nsteps) HIPCHK(hipMemcpyAsync(nsteps, e->d.nsteps, (size_t)4 * e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-extern "C" int gc_env_get_states(gc_env* e, int8_t* boards, uint8_t* meta) {
-    if (!e) return fail("null env");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    k_export<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, e->mbox, e->m8);
-    HIPCHK(hipGetLastError());
-    if (boards) HIPCHK(hipMemcpyAsync(boards, e->mbox, (size_t)64 * e->n, hipMemcpyDeviceToHost, e->stream));
-    if (meta) HIPCHK(hipMemcpyAsync(meta, e->m8, (size_t)8 * e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// set states (FEN/dict ingest). meta8[7] = move_count; repetition windows are cleared.
-extern "C" int gc_env_set_states(gc_env* e, const int8_t* boards, const uint8_t* meta) {
-    if (!e || !boards || !meta) return fail("null argument");
-    SRV_QUIESCE(e);
-    if (check_boards(e->n, boards)) return -1;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->mbox, boards, (size_t)64 * e->n, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->m8, meta, (size_t)8 * e->n, hipMemcpyHostToDevice, e->stream));
-    if (e->rules) k_fenv_import<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, nullptr, e->d);
-    else k_env_import<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, e->d, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (spill_windows_cleared(e)) return -1;
-    e->policy_ready = false;
-    return 0;
-}
-
-// ----------------------------------------------------------------------------- FEN
-// Forsyth-Edwards ingest/export for the reference's state: piece
-// placement rank 8 first (= board row 0, lib.rs:41-50), side to move, castling -> the four
-// *_castle_is_possible flags; en passant and the half-move clock do not exist under the
-// reference's rules and are ignored; the full-move number n maps to move_count = n - 1
-// (chess_v2.py:291-292 counts completed full moves).  Host code, no GPU needed.
-static const char* FEN_PIECES = ".KQRBNP";
-
-extern "C" int gc_fen_to_state(const char* fen, int8_t* board, uint8_t* meta) {
-    return gc_fen_to_state_rules(fen, board, meta, 0);
-}
-
-// rules 1 (FIDE): the en-passant field is parsed (it must be on the rank the side to move
-// captures onto) and meta8[7] = its file + 1 (0 = "-"), the engine's FIDE convention
-extern "C" int gc_fen_to_state_rules(const char* fen, int8_t* board, uint8_t* meta, int rules) {
-    if (!fen || !board || !meta) return fail("null argument");
-    int8_t b[64] = {0};
-    const char* p = fen;
-    while (*p == ' ') p++;
-    int row = 0, col = 0;
-    for (; *p && *p != ' '; p++) {
-        char c = *p;
-        if (c == '/') {
-            if (col != 8 || row >= 7) return fail(std::string("FEN: bad rank at '") + fen + "'");
-            row++;
-            col = 0;
-        } else if (c >= '1' && c <= '8') {
-            col += c - '0';
-            if (col > 8) return fail(std::string("FEN: rank overflow in '") + fen + "'");
-        } else {
-            const char* q = strchr(FEN_PIECES + 1, c >= 'a' ? c - 32 : c);
-            if (!q || c == '.' || col >= 8) return fail(std::string("FEN: bad piece '") + c + "' in '" + fen + "'");
-            int id = (int)(q - FEN_PIECES);
-            b[row * 8 + col++] = (int8_t)(c >= 'a' ? -id : id);
-        }
-    }
-    if (row != 7 || col != 8) return fail(std::string("FEN: placement must have 8 full ranks: '") + fen + "'");
-    uint8_t m[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-    while (*p == ' ') p++;
-    if (*p) {
-        if (*p == 'b') m[0] = 0;
-        else if (*p != 'w') return fail(std::string("FEN: side to move must be w or b: '") + fen + "'");
-        p++;
-        while (*p == ' ') p++;
-        for (; *p && *p != ' '; p++) {
-            switch (*p) {
-                case 'K': m[1] = 1; break;
-                case 'Q': m[2] = 1; break;
-                case 'k': m[3] = 1; break;
-                case 'q': m[4] = 1; break;
-                case '-': break;
-                default: return fail(std::string("FEN: bad castling field in '") + fen + "'");
-            }
-        }
-        // reference rules: en passant and half-move clock ignored, full-move number ->
-        // move_count; FIDE: en passant -> meta8[7]
-        int field = 0;
-        long full = 1;
-        int epf = -1;
-        while (*p) {
-            while (*p == ' ') p++;
-            if (!*p) break;
-            const char* st = p;
-            while (*p && *p != ' ') p++;
-            ++field;
-            if (field == 1 && rules && !(p - st == 1 && *st == '-')) {
-                int want = m[0] ? '6' : '3';
-                if (p - st != 2 || st[0] < 'a' || st[0] > 'h' || st[1] != want)
-                    return fail(std::string("FEN: bad en-passant field in '") + fen + "'");
-                epf = st[0] - 'a';
-            }
-            if (field == 3) {
-                char* end = nullptr;
-                full = strtol(st, &end, 10);
-                if (end != p || full < 1) return fail(std::string("FEN: bad full-move number in '") + fen + "'");
-            }
-        }
-        long mc = full - 1;
-        m[7] = rules ? (uint8_t)(epf + 1) : (uint8_t)(mc > 255 ? 255 : mc);
-    }
-    memcpy(board, b, 64);
-    memcpy(meta, m, 8);
-    return 0;
-}
-
-extern "C" int gc_state_to_fen(const int8_t* board, const uint8_t* meta, char* out, int cap) {
-    return gc_state_to_fen_rules(board, meta, out, cap, 0);
-}
-
-extern "C" int gc_state_to_fen_rules(const int8_t* board, const uint8_t* meta, char* out, int cap, int rules) {
-    if (!board || !meta || !out) return fail("null argument");
-    if (check_boards(1, board)) return -1;
-    std::string f;
-    for (int r = 0; r < 8; r++) {
-        int gap = 0;
-        for (int c = 0; c < 8; c++) {
-            int v = board[r * 8 + c];
-            if (!v) { gap++; continue; }
-            if (gap) { f += (char)('0' + gap); gap = 0; }
-            char ch = FEN_PIECES[v < 0 ? -v : v];
-            f += v < 0 ? (char)(ch + 32) : ch;
-        }
-        if (gap) f += (char)('0' + gap);
-        if (r < 7) f += '/';
-    }
-    f += meta[0] ? " w " : " b ";
-    std::string cs;
-    if (meta[1]) cs += 'K';
-    if (meta[2]) cs += 'Q';
-    if (meta[3]) cs += 'k';
-    if (meta[4]) cs += 'q';
-    f += cs.empty() ? "-" : cs;
-    if (rules) {
-        f += " ";
-        if (meta[7]) { f += (char)('a' + ((meta[7] - 1) & 7)); f += meta[0] ? '6' : '3'; }
-        else f += "-";
-        f += " 0 1";
-    } else {
-        f += " - 0 " + std::to_string((int)meta[7] + 1);
-    }
-    if ((int)f.size() + 1 > cap) return fail("FEN output buffer too small");
-    memcpy(out, f.c_str(), f.size() + 1);
-    return 0;
-}
-
-// FEN ingest for the whole env: boards[i] := fens[i], check flags from update_state,
-// repetition windows cleared (like gc_env_set_states)
-extern "C" int gc_env_set_fens(gc_env* e, const char* const* fens) {
-    if (!e || !fens) return fail("null argument");
-    SRV_QUIESCE(e);
-    std::vector<int8_t> b((size_t)64 * e->n), ep(e->n, -1);
-    std::vector<uint8_t> m((size_t)8 * e->n);
-    for (int i = 0; i < e->n; i++) {
-        uint8_t* mi = m.data() + 8 * (size_t)i;
-        if (gc_fen_to_state_rules(fens[i], b.data() + 64 * (size_t)i, mi, e->rules))
-            return fail("board " + std::to_string(i) + ": " + g_err);
-        if (e->rules) {  // meta8[7] carried the en-passant file: the env keeps move_count 0
-            ep[i] = (int8_t)(mi[7] ? mi[7] - 1 : -1);
-            mi[7] = 0;
-        }
-    }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->mbox, b.data(), b.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->m8, m.data(), m.size(), hipMemcpyHostToDevice, e->stream));
-    if (e->rules) {
-        if (!e->ep && dalloc(&e->ep, e->n)) return -1;
-        HIPCHK(hipMemcpyAsync(e->ep, ep.data(), e->n, hipMemcpyHostToDevice, e->stream));
-        k_fenv_import<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, e->ep, e->d);
-    } else {
-        k_env_import<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->mbox, e->m8, e->d, 1);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->policy_ready = false;
-    return 0;
-}
-
-extern "C" int gc_env_legal_moves(gc_env* e, uint16_t* moves, int cap, int32_t* counts) {
-    if (!e || !moves || !counts) return fail("null argument");
-    SRV_QUIESCE(e);
-    if (cap <= 0) return fail("cap must be > 0");
-    HIPCHK(hipSetDevice(e->device));
-    if (cap > e->list_cap) {
-        if (e->list) (void)hipFree(e->list);
-        e->list = nullptr;
-        e->list_cap = 0;
-        if (dalloc(&e->list, (size_t)cap * e->n)) return -1;
-        e->list_cap = cap;
-    }
-    if (e->rules) k_flist<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, 0, cap, e->list, e->counts);
-    else k_list<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, 0, cap, e->list, e->counts);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(moves, e->list, (size_t)2 * cap * e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(counts, e->counts, (size_t)4 * e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-extern "C" int gc_env_legal_mask(gc_env* e, uint64_t* mask, int32_t* counts) {
-    if (!e || !mask) return fail("null argument");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->lmask && dalloc(&e->lmask, (size_t)65 * e->n)) return -1;
-    if (e->rules) k_fmask<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, e->lmask, e->counts);
-    else k_mask<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, e->lmask, e->counts);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(mask, e->lmask, (size_t)8 * 65 * e->n, hipMemcpyDeviceToHost, e->stream));
-    if (counts) HIPCHK(hipMemcpyAsync(counts, e->counts, (size_t)4 * e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// Wait for the env's stream.  Spin on hipStreamQuery first (bounded): a blocking
-// hipStreamSynchronize can sleep on the completion interrupt and pays its wake-up on every
-// short wait; after GC_SPIN_US (default 20 000 us) of spinning it blocks.
-extern "C" int gc_env_synchronize(gc_env* e) {
-    if (!e) return fail("null env");
-    HIPCHK(hipSetDevice(e->device));
-    static const long spin_us = getenv("GC_SPIN_US") ? atol(getenv("GC_SPIN_US")) : 20000;
-    if (spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q == hipSuccess) return 0;
-            if (q != hipErrorNotReady) return fail(std::string("stream: ") + hipGetErrorString(q));
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us)) break;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-// Wait for the work of the last gc_env_rollout_device call: when it ended with a quad launch,
-// until that launch's completion word reaches host memory (every workgroup's stores done),
-// else until the stream is idle.  Work enqueued after the launch (an event record) may still
-// be pending; reads through the env's stream stay ordered after it.  Spins with a stream
-// query now and then, so a word that never comes cannot hang the caller.
-extern "C" int gc_env_wait_rollout(gc_env* e) {
-    if (!e) return fail("null env");
-    if (!e->done_expect || !e->done_host) return gc_env_synchronize(e);
-    const u32 want = e->done_expect;
-    for (unsigned k = 0;; k++) {
-        if ((int)(__atomic_load_n(e->done_host, __ATOMIC_ACQUIRE) - want) >= 0) return 0;
-        if ((k & 255) == 255) {
-            const hipError_t q = hipStreamQuery(e->stream);
-            if (q == hipSuccess) return 0;
-            if (q != hipErrorNotReady) return fail(std::string("stream: ") + hipGetErrorString(q));
-        }
-    }
-}
-
-extern "C" int gc_env_record_event(gc_env* e, int slot) {
-    if (!e || slot < 0 || slot >= 8) return fail("bad env or event slot");
-    HIPCHK(hipEventRecord(e->ev[slot], e->stream));
-    return 0;
-}
-
-extern "C" int gc_env_elapsed_ms(gc_env* e, int a, int b, float* ms) {
-    if (!e || !ms || a < 0 || a >= 8 || b < 0 || b >= 8) return fail("bad argument");
-    HIPCHK(hipEventSynchronize(e->ev[b]));
-    HIPCHK(hipEventElapsedTime(ms, e->ev[a], e->ev[b]));
-    return 0;
-}
-
-// sum over boards of the repetition-window length (bytes accounting in bench.py)
-__global__ void k_window_sum(SoA st, unsigned long long* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long v = i < st.n ? (unsigned long long)hl_of(st.meta[i]) : 0ull;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
-}
-
-extern "C" int gc_env_window_sum(gc_env* e, uint64_t* sum) {
-    if (!e || !sum) return fail("null argument");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    unsigned long long* d = nullptr;
-    if (dalloc(&d, 1)) return -1;
-    HIPCHK(hipMemsetAsync(d, 0, 8, e->stream));
-    k_window_sum<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, d);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(sum, d, 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    (void)hipFree(d);
-    return 0;
-}
-
-#ifdef GC_PSTAMPS
-// per wave (global wave index = block * waves per block + wave): the 8 segment cycle sums of
-// one fused launch of n_plies (reference rules, opponent "none"), then 4 s_memrealtime stamps:
-// wave start, entry loads done, first ply done, last ply done
-extern "C" int gc_debug_pstamps(gc_env* e, int n_plies, uint64_t* out /* waves * 12 */) {
-    unsigned long long* d = nullptr;
-    // waves of the fused launch: pairs (2 per 64 boards) or quads (4 per 64 boards)
-    const size_t waves = use_quad(e) ? (size_t)((e->n + QUAD_BOARDS * QUADS_WG - 1) / (QUAD_BOARDS * QUADS_WG)) * 4 * QUADS_WG
-                                     : (size_t)((e->n + PAIR_BOARDS * PAIRS_WG - 1) / (PAIR_BOARDS * PAIRS_WG)) * 2 * PAIRS_WG;
-    if (dalloc(&d, waves * 12)) return -1;
-    HIPCHK(hipMemsetAsync(d, 0, waves * 96, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &d, sizeof(d)));
-    if (issue_rollout(e, n_plies, nullptr, false)) return -1;
-    HIPCHK(hipMemcpyAsync(out, d, waves * 96, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    unsigned long long* z = nullptr;
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &z, sizeof(z)));
-    (void)hipFree(d);
-    return 0;
-}
-#endif
-
-#ifdef GC_PSTAMPS
-// the quad API step's per-wave stamps (tools/api_pstamp_probe.py): buffer on (`on` != 0, sized
-// for the env's k_env_step_api4 waves, zeroed) or copied out and off
-static unsigned long long* g_api_pst = nullptr;
-extern "C" int gc_debug_api_pstamps(gc_env* e, int on, uint64_t* out /* waves * 12 */) {
-    const size_t waves = (size_t)((e->n + QUAD_BOARDS * QUADS_WG - 1) / (QUAD_BOARDS * QUADS_WG)) * 4 * QUADS_WG;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (on) {
-        if (!g_api_pst && dalloc(&g_api_pst, waves * 12)) return -1;
-        HIPCHK(hipMemset(g_api_pst, 0, waves * 96));
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &g_api_pst, sizeof(g_api_pst)));
-        return 0;
-    }
-    if (g_api_pst && out) HIPCHK(hipMemcpy(out, g_api_pst, waves * 96, hipMemcpyDeviceToHost));
-    unsigned long long* z = nullptr;
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &z, sizeof(z)));
-    return 0;
-}
-#endif
-
-#ifdef GC_STAMPS
-extern "C" int gc_debug_stamps(gc_env* e, int n_plies, uint64_t* out /* (n/64)*8 */) {
-    unsigned long long* d = nullptr;
-    size_t cnt = (size_t)((e->n + 63) / 64) * 16;  // per wave: 8 stamps (the paired kernel has 2 waves / 64 boards)
-    if (dalloc(&d, cnt)) return -1;
-    HIPCHK(hipMemsetAsync(d, 0, cnt * 8, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_out), &d, sizeof(d)));
-    for (int p = 0; p < n_plies; p++) {
-        launch_step2(e, e->stream);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, d, cnt * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    unsigned long long* z = nullptr;
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_out), &z, sizeof(z)));
-    (void)hipFree(d);
-    return 0;
-}
-#endif
-
-// en passant of the FIDE-rules env (gc_fide.h keeps it in meta bits 25..28; the env's
-// meta8[7] is move_count, so it travels beside the state arrays)
-__global__ void k_get_ep(SoA st, int8_t* __restrict__ files) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= st.n) return;
-    u32 m = st.meta[i];
-    files[i] = (m & gcf::M_EP) ? (int8_t)((m & gcf::M_EP_MASK) >> gcf::M_EP_SHIFT) : (int8_t)-1;
-}
-__global__ void k_set_ep(SoA st, const int8_t* __restrict__ files) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= st.n) return;
-    st.meta[i] = gcf::with_ep(st.meta[i], files[i] < 0 ? -1 : (int)files[i]);
-}
-
-extern "C" int gc_env_get_en_passant(gc_env* e, int8_t* files) {
-    if (!e || !files) return fail("null argument");
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->ep && dalloc(&e->ep, e->n)) return -1;
-    k_get_ep<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, e->ep);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(files, e->ep, e->n, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return 0;
-}
-
-extern "C" int gc_env_set_en_passant(gc_env* e, const int8_t* files) {
-    if (!e || !files) return fail("null argument");
-    for (int i = 0; i < e->n; i++) {
-        if (files[i] > 7) return fail("en-passant file out of range at index " + std::to_string(i));
-        if (files[i] >= 0 && !e->rules) return fail("en passant exists only under rules=fide (Q3: the reference has none)");
-    }
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->ep && dalloc(&e->ep, e->n)) return -1;
-    HIPCHK(hipMemcpyAsync(e->ep, files, e->n, hipMemcpyHostToDevice, e->stream));
-    k_set_ep<<<grid_for(e->n), BLOCK, 0, e->stream>>>(e->d.st, e->ep);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->policy_ready = false;
-    return 0;
-}
-
-// ----------------------------------------------------------------------------- checkpoint
-// Bit-exact save / restore of a whole env (SURVEY.md §5 "save/load = memcpy of state +
-// repetition history"; the reference keeps its history in ChessEnvV2.saved_boards,
-// chess_v2.py:192, 404-407, beside the state dict, 301-323).  Blob layout (version 2):
-//   CkptHeader | slab (Slab::BYTES_PER_BOARD * n: bitboards, meta, window generation, Philox
-//   draw counter, step counter, last outputs, next action) | spill counts u32[n] (live spill
-//   entries per board, zero unless a BLACK agent's window spilled) | the live window-table
-//   entries, board by board (hl_of(meta[i]) entries of 8 u64: header {tag | count << 56}, 7
-//   bitboards) | the live spill entries, board by board (8 u64: count, 7 bitboards).
-// Only live entries travel: restoring re-inserts them under a fresh generation, so a restored
-// board answers every later probe exactly as before (same boards, same counts; slot positions
-// may differ, which no result depends on).  The header pins the slab's field layout
-// (CKPT_LAYOUT); a blob whose windows do not fit the env's tables is refused before anything
-// of the env changes.
-struct CkptHeader {
-    char magic[8];  // "GCCKPT2"
-    uint32_t version, n, rules, opp, agent_black, policy_ready;
-    uint64_t seed;
-    uint64_t init[NBB];  // the env's initial board (resets land on it)
-    uint64_t entries;        // window-table entries
-    uint64_t spill_entries;  // spill-table entries
-    uint64_t layout;         // CKPT_LAYOUT of the writer
-};
-static const char CKPT_MAGIC[8] = {'G', 'C', 'C', 'K', 'P', 'T', '2', 0};
-// the slab's size and field offsets per board (a writer with another layout is refused)
-static constexpr uint64_t CKPT_LAYOUT = (uint64_t)Slab::BYTES_PER_BOARD | (56ull << 8) | (60ull << 16) | (64ull << 24) |
-                                        (68ull << 32) | (72ull << 40) | (76ull << 48) | (78ull << 56);
-static_assert(Slab::BYTES_PER_BOARD == 80, "update CKPT_LAYOUT with the slab");
-
-__global__ void k_hl_of(const u32* __restrict__ meta, int n, uint32_t* __restrict__ hl) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) hl[i] = hl_of(meta[i]);
-}
-
-// the live entries (generation == hgen[i]) of board i, in table order, at out[offs[i]..]
-__global__ void k_ckpt_pack(const u64* __restrict__ htab, const u32* __restrict__ hgen, const u32* __restrict__ meta,
-                            int n, int nb, const uint32_t* __restrict__ offs, u64* __restrict__ out,
-                            uint32_t* __restrict__ bad) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    DevHist h{const_cast<u64*>(htab), const_cast<u32*>(hgen), hgen[i], i, nb};
-    const u32 g = h.gen(), hl = hl_of(meta[i]);
-    u32 k = 0;
-    u64* o = out + (size_t)offs[i] * 8;
-    for (int pos = 0; pos < (1 << nb); pos++) {
-        const u64* e = htab + h.entry(pos) * 8;
-        u64 hdr = e[0];
-        if ((u32)hdr != g) continue;
-        if (k < hl) {
-            u64* d = o + (size_t)k * 8;
-            d[0] = hdr & ~0xFFFFFFFFull;  // tag | count; the generation is re-issued on restore
-#pragma unroll
-            for (int j = 1; j < 8; j++) d[j] = e[j];
-        }
-        k++;
-    }
-    if (k != hl) atomicOr(bad, 1u);
-}
-
-// live spill entries per board (cnt zeroed by the caller); with out: packed at
-// out[offs[owner] + fill[owner]++] as {count, 7 bitboards}
-__global__ void k_spill_collect(const u64* __restrict__ ent, u32 mask, const u32* __restrict__ hgen,
-                                uint32_t* __restrict__ cnt, const uint32_t* __restrict__ offs, u64* __restrict__ out) {
-    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot > mask) return;
-    const u64* e = ent + slot * 8;
-    const u64 hdr = e[0];
-    const u32 o1 = sp_owner1(hdr);
-    if (o1 == 0 || sp_gen(hdr) != hgen[o1 - 1]) return;
-    const u32 k = atomicAdd(cnt + (o1 - 1), 1u);
-    if (!out) return;
-    u64* d = out + ((size_t)offs[o1 - 1] + k) * 8;
-    d[0] = sp_cnt(hdr);
-#pragma unroll
-    for (int j = 1; j < 8; j++) d[j] = e[j];
-}
-
-// fresh generation per board: above both the live table's and the saved one, so no entry of
-// the live table can pass for a restored one
-__global__ void k_ckpt_gen(const u32* __restrict__ live_hgen, const u32* __restrict__ saved_hgen, int n,
-                           uint32_t* __restrict__ gnew) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) gnew[i] = (live_hgen[i] > saved_hgen[i] ? live_hgen[i] : saved_hgen[i]) + 1u;
-}
-
-// refuse a blob whose windows do not fit the env's tables (before the env changes): a window
-// longer than hist_cap, or spill entries without a full table or without a spill table
-__global__ void k_ckpt_check(const u32* __restrict__ meta, const uint32_t* __restrict__ scnt, int n, int nb, int spill,
-                             uint32_t* __restrict__ bad) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int hl = (int)hl_of(meta[i]);
-    if (hl > hist_cap(nb)) atomicOr(bad, 1u);
-    if (scnt[i] && (!spill || hl < hist_cap(nb))) atomicOr(bad, 2u);
-}
-
-// board i takes generation gnew[i] and its saved entries are inserted by the probe rule of
-// rep_commit (gc_env.h): home slot = key & (HTAB-1), linear probing; its spill entries by
-// spill_insert's
-__global__ void k_ckpt_unpack(u64* __restrict__ htab, u32* __restrict__ hgen, const u32* __restrict__ meta, int n,
-                              int nb, const uint32_t* __restrict__ gnew, const uint32_t* __restrict__ offs,
-                              const u64* __restrict__ in, SpillTab sp, const uint32_t* __restrict__ scnt,
-                              const uint32_t* __restrict__ soffs, const u64* __restrict__ sin, uint32_t* __restrict__ bad) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u32 g = gnew[i];
-    hgen[i] = g;
-    DevHist h{htab, hgen, g, i, nb};
-    h.sp = sp;
-    const u32 hl = hl_of(meta[i]);
-    const int size = 1 << nb;
-    for (u32 k = 0; k < hl; k++) {
-        const u64* e = in + ((size_t)offs[i] + k) * 8;
-        Pos b = {e[1], e[2], e[3], e[4], e[5], e[6], e[7], 0};
-        u32 key = board_key(b);
-        u32 pos = key & (size - 1), tag = key >> nb;
-        int probe = 0;
-        while ((u32)htab[h.entry((int)pos) * 8] == g && probe < size) { pos = (pos + 1) & (size - 1); probe++; }
-        if (probe == size) { atomicOr(bad, 2u); return; }
-        u64* d = htab + h.entry((int)pos) * 8;
-        d[0] = (u64)g | ((u64)tag << 32) | (e[0] & (0xFFull << 56));
-#pragma unroll
-        for (int j = 1; j < 8; j++) d[j] = e[j];
-    }
-    for (u32 k = 0; k < (scnt ? scnt[i] : 0u); k++) {
-        const u64* e = sin + ((size_t)soffs[i] + k) * 8;
-        Pos b = {e[1], e[2], e[3], e[4], e[5], e[6], e[7], 0};
-        if (!spill_insert(h, b, board_key(b))) { atomicOr(bad, 4u); return; }
-        u32 t = sp_home(board_key(b), (u32)i, sp.mask);  // the entry just inserted: set its count
-        for (int probe = 0; probe < SPILL_PROBES; probe++, t = (t + 1) & sp.mask) {
-            const u64 x = h.sp_hdr(t);
-            if (sp_owner1(x) == (u32)i + 1 && sp_gen(x) == g && h.sp_same(t, b)) {
-                h.sp_set_hdr(t, sp_make((u32)i, g, (u32)e[0]));
-                break;
-            }
-        }
-    }
-}
-
-// exclusive scan of v (n entries) -> offs; returns the total
-static int scan_u32(gc_env* e, const uint32_t* v, uint32_t* offs, int n, uint64_t* total) {
-    size_t tb = 0;
-    void* tmp = nullptr;
-    hipError_t he = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, v, offs, n, e->stream);
-    if (he == hipSuccess && dalloc((char**)&tmp, tb ? tb : 1)) return -1;
-    if (he == hipSuccess) he = hipcub::DeviceScan::ExclusiveSum(tmp, tb, v, offs, n, e->stream);
-    uint32_t lo = 0, lc = 0;
-    if (he == hipSuccess) he = hipMemcpyAsync(&lo, offs + n - 1, 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(&lc, v + n - 1, 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    (void)hipFree(tmp);
-    if (he != hipSuccess) return fail(std::string("checkpoint scan: ") + hipGetErrorString(he));
-    *total = (uint64_t)lo + lc;
-    return 0;
-}
-
-// exclusive scan of the window lengths of `meta` (the saved or live slab's) -> offs; returns
-// the total entry count
-static int ckpt_offsets(gc_env* e, const u32* meta, uint32_t* hl, uint32_t* offs, uint64_t* total) {
-    k_hl_of<<<grid_for(e->n), BLOCK, 0, e->stream>>>(meta, e->n, hl);
-    return scan_u32(e, hl, offs, e->n, total);
-}
-
-// live spill entries per board (scnt) and their offsets (soffs); total
-static int spill_offsets(gc_env* e, uint32_t* scnt, uint32_t* soffs, uint64_t* total) {
-    HIPCHK(hipMemsetAsync(scnt, 0, (size_t)4 * e->n, e->stream));
-    const SpillTab& sp = e->d.ic.spill;
-    if (sp.ent) {
-        const size_t slots = (size_t)sp.mask + 1;
-        k_spill_collect<<<(unsigned)((slots + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(sp.ent, sp.mask, e->d.hgen, scnt,
-                                                                                          nullptr, nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    return scan_u32(e, scnt, soffs, e->n, total);
-}
-
-static size_t ckpt_bytes(int n, uint64_t entries, uint64_t spill_entries) {
-    return sizeof(CkptHeader) + (Slab::BYTES_PER_BOARD + 4) * (size_t)n + 64 * (size_t)(entries + spill_entries);
-}
-
-extern "C" int gc_env_checkpoint_bytes(gc_env* e, uint64_t* bytes) {
-    if (!e || !bytes) return fail("null argument");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    uint32_t *hl = nullptr, *offs = nullptr;
-    if (dalloc(&hl, e->n) || dalloc(&offs, e->n)) { (void)hipFree(hl); return -1; }
-    uint64_t total = 0, stotal = 0;
-    int rc = ckpt_offsets(e, e->meta, hl, offs, &total);
-    if (!rc) rc = spill_offsets(e, hl, offs, &stotal);
-    (void)hipFree(hl); (void)hipFree(offs);
-    if (rc) return rc;
-    *bytes = ckpt_bytes(e->n, total, stotal);
-    return 0;
-}
-
-extern "C" int gc_env_save(gc_env* e, void* buf, uint64_t cap, uint64_t* written) {
-    if (!e || !buf) return fail("null argument");
-    SRV_QUIESCE(e);
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const int n = e->n;
-    uint32_t *hl = nullptr, *offs = nullptr, *bad = nullptr, *scnt = nullptr, *soffs = nullptr, *fill = nullptr;
-    u64 *ents = nullptr, *sents = nullptr;
-    auto release = [&]() {
-        (void)hipFree(hl); (void)hipFree(offs); (void)hipFree(bad); (void)hipFree(ents);
-        (void)hipFree(scnt); (void)hipFree(soffs); (void)hipFree(fill); (void)hipFree(sents);
-    };
-    if (dalloc(&hl, n) || dalloc(&offs, n) || dalloc(&bad, 1) || dalloc(&scnt, n) || dalloc(&soffs, n) ||
-        dalloc(&fill, n)) { release(); return -1; }
-    uint64_t total = 0, stotal = 0;
-    if (ckpt_offsets(e, e->meta, hl, offs, &total) || spill_offsets(e, scnt, soffs, &stotal)) { release(); return -1; }
-    const size_t need = ckpt_bytes(n, total, stotal);
-    if (written) *written = need;
-    if (cap < need) { release(); return fail("checkpoint buffer too small: need " + std::to_string(need) + " bytes"); }
-    if (dalloc(&ents, 8 * (total ? total : 1)) || dalloc(&sents, 8 * (stotal ? stotal : 1))) { release(); return -1; }
-    CkptHeader hd = {};
-    memcpy(hd.magic, CKPT_MAGIC, 8);
-    hd.version = 2; hd.n = (uint32_t)n; hd.rules = (uint32_t)e->rules; hd.opp = (uint32_t)e->d.opp;
-    hd.agent_black = (uint32_t)e->d.agent_black; hd.policy_ready = e->policy_ready ? 1u : 0u;
-    hd.seed = e->seed;
-    for (int j = 0; j < NBB; j++) hd.init[j] = e->d.init[j];
-    hd.entries = total;
-    hd.spill_entries = stotal;
-    hd.layout = CKPT_LAYOUT;
-    uint8_t* out = static_cast<uint8_t*>(buf);
-    memcpy(out, &hd, sizeof hd);
-    const size_t o_slab = sizeof hd, o_scnt = o_slab + Slab::BYTES_PER_BOARD * (size_t)n, o_ent = o_scnt + 4 * (size_t)n,
-                 o_sent = o_ent + 64 * (size_t)total;
-    uint32_t flag = 0;
-    hipError_t he = hipMemsetAsync(bad, 0, 4, e->stream);
-    if (he == hipSuccess) {
-        k_ckpt_pack<<<grid_for(n), BLOCK, 0, e->stream>>>(e->d.htab, e->d.hgen, e->meta, n, e->d.hbits, offs, ents, bad);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess && stotal) {
-        const SpillTab& sp = e->d.ic.spill;
-        const size_t slots = (size_t)sp.mask + 1;
-        he = hipMemsetAsync(fill, 0, (size_t)4 * n, e->stream);
-        if (he == hipSuccess) {
-            k_spill_collect<<<(unsigned)((slots + BLOCK - 1) / BLOCK), BLOCK, 0, e->stream>>>(sp.ent, sp.mask, e->d.hgen,
-                                                                                              fill, soffs, sents);
-            he = hipGetLastError();
-        }
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(out + o_slab, e->slab, Slab::BYTES_PER_BOARD * (size_t)n, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(out + o_scnt, scnt, 4 * (size_t)n, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess && total) he = hipMemcpyAsync(out + o_ent, ents, 64 * total, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess && stotal) he = hipMemcpyAsync(out + o_sent, sents, 64 * stotal, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(&flag, bad, 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    release();
-    if (he != hipSuccess) return fail(std::string("checkpoint save: ") + hipGetErrorString(he));
-    if (flag) return fail("checkpoint save: a repetition window does not match its recorded length");
-    return 0;
-}
-
-extern "C" int gc_env_load(gc_env* e, const void* buf, uint64_t size) {
-    if (!e || !buf) return fail("null argument");
-    SRV_QUIESCE(e);
-    if (size < sizeof(CkptHeader)) return fail("checkpoint: truncated header");
-    CkptHeader hd;
-    memcpy(&hd, buf, sizeof hd);
-    if (memcmp(hd.magic, CKPT_MAGIC, 8) != 0 || hd.version != 2) return fail("checkpoint: not a gc_env checkpoint (v2)");
-    if (hd.layout != CKPT_LAYOUT) return fail("checkpoint: written by a build with another slab layout");
-    if ((int)hd.n != e->n) return fail("checkpoint: it holds " + std::to_string(hd.n) + " boards, the env " + std::to_string(e->n));
-    if ((int)hd.rules != e->rules || (int)hd.opp != e->d.opp || (int)hd.agent_black != e->d.agent_black)
-        return fail("checkpoint: rules / opponent / player colour differ from the env's");
-    if (hd.seed != e->seed) return fail("checkpoint: the env's seed differs (the policy streams would not continue)");
-    for (int j = 0; j < NBB; j++)
-        if (hd.init[j] != e->d.init[j]) return fail("checkpoint: the env's initial board differs");
-    if (size != ckpt_bytes(e->n, hd.entries, hd.spill_entries)) return fail("checkpoint: size does not match its header");
-    if (hd.spill_entries && !e->d.ic.spill.ent) return fail("checkpoint: spill entries, but the env has no spill table");
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const int n = e->n;
-    const uint8_t* in = static_cast<const uint8_t*>(buf);
-    const size_t o_slab = sizeof hd, o_scnt = o_slab + Slab::BYTES_PER_BOARD * (size_t)n, o_ent = o_scnt + 4 * (size_t)n,
-                 o_sent = o_ent + 64 * (size_t)hd.entries;
-    uint8_t* slab = nullptr;
-    u64 *ents = nullptr, *sents = nullptr;
-    uint32_t *hl = nullptr, *offs = nullptr, *gnew = nullptr, *bad = nullptr, *scnt = nullptr, *soffs = nullptr;
-    auto release = [&]() {
-        (void)hipFree(slab); (void)hipFree(ents); (void)hipFree(hl); (void)hipFree(offs); (void)hipFree(gnew);
-        (void)hipFree(bad); (void)hipFree(sents); (void)hipFree(scnt); (void)hipFree(soffs);
-    };
-    if (dalloc(&slab, Slab::BYTES_PER_BOARD * (size_t)n) || dalloc(&ents, 8 * (hd.entries ? hd.entries : 1)) ||
-        dalloc(&sents, 8 * (hd.spill_entries ? hd.spill_entries : 1)) || dalloc(&hl, n) || dalloc(&offs, n) ||
-        dalloc(&gnew, n) || dalloc(&bad, 1) || dalloc(&scnt, n) || dalloc(&soffs, n)) {
-        release();
-        return -1;
-    }
-    // stage everything and validate it against the env's tables before touching the env
-    hipError_t he = hipMemcpyAsync(slab, in + o_slab, Slab::BYTES_PER_BOARD * (size_t)n, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(scnt, in + o_scnt, 4 * (size_t)n, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess && hd.entries)
-        he = hipMemcpyAsync(ents, in + o_ent, 64 * hd.entries, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess && hd.spill_entries)
-        he = hipMemcpyAsync(sents, in + o_sent, 64 * hd.spill_entries, hipMemcpyHostToDevice, e->stream);
-    if (he != hipSuccess) { release(); return fail(std::string("checkpoint load: ") + hipGetErrorString(he)); }
-    uint64_t total = 0, stotal = 0;
-    const u32* smeta = reinterpret_cast<const u32*>(slab + Slab::meta(n));
-    if (ckpt_offsets(e, smeta, hl, offs, &total) || scan_u32(e, scnt, soffs, n, &stotal)) { release(); return -1; }
-    if (total != hd.entries || stotal != hd.spill_entries) {
-        release();
-        return fail("checkpoint: window lengths do not match the entries it holds");
-    }
-    uint32_t flag = 0;
-    he = hipMemsetAsync(bad, 0, 4, e->stream);
-    if (he == hipSuccess) {
-        k_ckpt_check<<<grid_for(n), BLOCK, 0, e->stream>>>(smeta, scnt, n, e->d.hbits, e->d.ic.spill.ent != nullptr, bad);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(&flag, bad, 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he != hipSuccess || flag) {
-        release();
-        return fail(he != hipSuccess ? std::string("checkpoint load: ") + hipGetErrorString(he)
-                                     : std::string("checkpoint: its repetition windows do not fit this env's tables"));
-    }
-    // the spill table, emptied (every entry would be dead under the fresh generations) and
-    // sized for the restored entries at a load <= 1/8
-    if (e->d.ic.spill.ent) {
-        int bits = e->sp_bits;
-        while (((uint64_t)1 << bits) < 8 * stotal) bits++;
-        if (spill_alloc(e, bits)) { release(); return -1; }
-    }
-    // from here on the env changes; a failure resets every board (never a half-restored env)
-    k_ckpt_gen<<<grid_for(n), BLOCK, 0, e->stream>>>(e->d.hgen, reinterpret_cast<const u32*>(slab + Slab::hgen(n)), n,
-                                                     gnew);
-    he = hipGetLastError();
-    if (he == hipSuccess)
-        he = hipMemcpyAsync(e->slab, slab, Slab::BYTES_PER_BOARD * (size_t)n, hipMemcpyDeviceToDevice, e->stream);
-    if (he == hipSuccess) he = hipMemsetAsync(bad, 0, 4, e->stream);
-    if (he == hipSuccess) {
-        k_ckpt_unpack<<<grid_for(n), BLOCK, 0, e->stream>>>(e->d.htab, e->d.hgen, e->meta, n, e->d.hbits, gnew, offs,
-                                                            ents, e->d.ic.spill, stotal ? scnt : nullptr, soffs, sents,
-                                                            bad);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(&flag, bad, 4, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    release();
-    if (he != hipSuccess || flag) {
-        std::string m = he != hipSuccess ? std::string("checkpoint load: ") + hipGetErrorString(he)
-                                         : std::string("checkpoint load: a repetition window did not fit the table");
-        if (he == hipSuccess) {  // the env is half-restored: start every board afresh
-            launch_reset(e, nullptr, 1);
-            (void)hipStreamSynchronize(e->stream);
-            e->policy_ready = true;
-            m += " (every board was reset)";
-        }
-        return fail(m);
-    }
-    e->policy_ready = hd.policy_ready != 0;
-    return 0;
-}
-
-// bytes of device memory held by the env (for reports)
-extern "C" uint64_t gc_env_device_bytes(gc_env* e) {
-    if (!e) return 0;
-    uint64_t n = (uint64_t)e->n;
-    return n * (NBB * 8 + 4) + n * ((uint64_t)64 << e->d.hbits) + n * (4 + 4 + 2 + 4 + 1 + 1 + 4) +
-           n * (64 + 8 + 1 + 4 + 64);
-}
+// ----------------------------------------------------------------------------- host side (the C ABI)
+#include "gc_fen.h"
+#include "gc_host_server.h"
+#include "gc_host_engine.h"
+#include "gc_host_perft.h"
+#include "gc_host_env_state.h"
+#include "gc_host_spill.h"
+#include "gc_host_env.h"
+#include "gc_host_ckpt.h"

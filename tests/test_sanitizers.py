@@ -27,3 +27,17 @@ def test_core_and_oracle_under_asan_ubsan(tmp_path):
     r = subprocess.run([str(exe), "300"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     assert "fails 0" in r.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_fen_codec_under_asan_ubsan(tmp_path):
+    """The C-ABI's FEN codec (csrc/gc_fen.h, plain C++) on valid, malformed and mutated strings
+    (tests/core_host/fen_sanitize_main.cpp)."""
+    exe = tmp_path / "fen_sanitize"
+    subprocess.run(["g++", "-std=c++17", "-Wno-unknown-pragmas", *SAN, "-o", str(exe),
+                    os.path.join(ROOT, "tests", "core_host", "fen_sanitize_main.cpp")], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
+               UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe), "3000"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "fails 0" in r.stdout
