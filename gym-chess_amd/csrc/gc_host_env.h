@@ -110,6 +110,8 @@ struct LaunchGeom {
 static int board_blocks(const gc_env* e) { return (e->n + PAIR_BOARDS - 1) / PAIR_BOARDS; }
 static LaunchGeom pair_geom(int nb) { return {dim3((nb + PAIRS_WG - 1) / PAIRS_WG), dim3(2 * PAIR_BOARDS * PAIRS_WG)}; }
 static LaunchGeom quad_geom(int nb) { return {dim3((nb + QUADS_WG - 1) / QUADS_WG), dim3(4 * QUAD_BOARDS * QUADS_WG)}; }
+// the quad rollout's own (k_env_rollout4<OCC, qw>: qw quads per workgroup, roll_quads_wg)
+static LaunchGeom roll_geom(int nb, int qw) { return {dim3((nb + qw - 1) / qw), dim3(4 * QUAD_BOARDS * qw)}; }
 
 // the paired kernels' <FIDE, OPP> variant for the env's rules and opponent, and the reset picks'
 // table it reads
@@ -673,6 +675,15 @@ static int occ_min_plies() {
 
 extern "C" int gc_env_rollout_occ_min_plies(void) { return occ_min_plies(); }
 
+// One quad per workgroup (k_env_rollout4<OCC, ROLL_QUADS_WG>: four workgroups per CU, each
+// waiting at its barriers for its own four waves only) runs the ply faster but starts twice
+// the workgroups.  Same box, 5 interleaved repeats, one / two quads per workgroup, us per ply
+// by events (profiles/r08_geometry/ab_ksweep.log): K = 20 4.66 / 4.41, 50 4.12 / 4.13, 100
+// 3.95 / 4.01, 200 3.92 / 4.00, 400 3.87 / 3.93, 600 3.91 / 4.08, 1 000 3.83 / 3.98 -- so
+// launches below ROLL_SPLIT_MIN_PLIES plies keep two quads per workgroup
+#define ROLL_SPLIT_MIN_PLIES 50
+static int roll_quads_wg(int plies) { return plies >= ROLL_SPLIT_MIN_PLIES ? ROLL_QUADS_WG : QUADS_WG; }
+
 extern "C" int gc_env_rollout_waves(gc_env* e) {
     if (!e) return fail("null env");
     return pair_ok(e) ? (use_quad(e) ? 4 : 2) : 1;
@@ -697,7 +708,7 @@ static int issue_rollout(gc_env* e, int n_plies, uint64_t* d_trace, bool stats) 
     const bool pair = pair_ok(e);
     const EnvDev& d = e->d;
     const ResetInfo r = reset_info(e);
-    const LaunchGeom pg = pair_geom(board_blocks(e)), qg = quad_geom(board_blocks(e));
+    const LaunchGeom pg = pair_geom(board_blocks(e));
     for (int p0 = 0, k = 0; p0 < n_plies; p0 += k) {
         k = spill_chunk(e, n_plies - p0 < ROLLOUT_MAX_PLIES ? n_plies - p0 : ROLLOUT_MAX_PLIES);
         if (k < 0) return -1;
@@ -705,7 +716,10 @@ static int issue_rollout(gc_env* e, int n_plies, uint64_t* d_trace, bool stats) 
         const u32 ri = r.rinfo | ((u32)k << 18);
         e->done_expect = 0;
         if (pair && use_quad(e)) {
-            const auto kernel = k >= occ_min_plies() ? k_env_rollout4<true> : k_env_rollout4<false>;
+            const bool occ = k >= occ_min_plies(), split = roll_quads_wg(k) == ROLL_QUADS_WG;
+            const LaunchGeom qg = roll_geom(board_blocks(e), roll_quads_wg(k));
+            const auto kernel = split ? (occ ? k_env_rollout4<true, ROLL_QUADS_WG> : k_env_rollout4<false, ROLL_QUADS_WG>)
+                                      : (occ ? k_env_rollout4<true, QUADS_WG> : k_env_rollout4<false, QUADS_WG>);
             kernel<<<qg.grid, qg.block, 0, e->stream>>>(e->slab, d.n, d.seed, d.htab, sw_table(r), r.icd, ri, st, tr);
             e->done_expect = ++e->done_issued;
         } else if (pair) {
@@ -979,7 +993,7 @@ extern "C" int gc_debug_pstamps(gc_env* e, int n_plies, uint64_t* out /* waves *
     Temps tmps;
     unsigned long long* d = nullptr;
     // waves of the fused launch: pairs (2 per 64 boards) or quads (4 per 64 boards)
-    const LaunchGeom g = use_quad(e) ? quad_geom(board_blocks(e)) : pair_geom(board_blocks(e));
+    const LaunchGeom g = use_quad(e) ? roll_geom(board_blocks(e), roll_quads_wg(n_plies)) : pair_geom(board_blocks(e));
     const size_t waves = (size_t)g.grid.x * (g.block.x / 64);
     if (tmps.alloc(&d, waves * 12)) return -1;
     HIPCHK(hipMemsetAsync(d, 0, waves * 96, e->stream));

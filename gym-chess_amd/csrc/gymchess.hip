@@ -2063,11 +2063,28 @@ __global__ void __launch_bounds__(2 * PAIR_BOARDS * PAIRS_WG) PAIR_ATTR
 // like the totals, when no generation is due.  Same decisions in the same order as
 // pair_ply (and so as k_env_step<true, false> and the oracle): tests/test_gpu_parity.py and
 // tests/test_full_size.py run the fused rollouts against the oracle and the launched kernel.
+//
+// Geometry (k_env_rollout4<OCC, QW>, QW quads per workgroup).  The four barriers of a ply wait
+// for a workgroup's waves, and two quads share no data, so a quad is a workgroup of its own
+// (QW = ROLL_QUADS_WG = 1: 256 threads, 34 KB of LDS, four workgroups per CU) and waits only
+// for its own slowest role: 9 900 vs 10 330 cycles per ply by stamps.  Every SIMD then hosts
+// all four roles, one of each workgroup of its CU (the dispatcher's placement: see the role
+// map in the kernel), and the four take weighted turns (ROLL_TURNS).  Twice the workgroups
+// cost a short launch more than the ply gains, so launches below ROLL_SPLIT_MIN_PLIES
+// (gc_host_env.h) keep QW = QUADS_WG = 2, where every SIMD hosts a state-carrying and a
+// stateless role of each workgroup.  tests/test_rollout_geometry_gpu.py runs both at 1-6
+// workgroups.
 #define QUAD_BOARDS 64
 #ifndef QUADS_WG
-#define QUADS_WG 2  // two quads per workgroup; the second's roles rotated by 2 so that every SIMD
-                    // hosts a state-carrying and a stateless role of each workgroup
+#define QUADS_WG 2  // the API steps: two quads per workgroup; the second's roles rotated by 2 so that
+                    // every SIMD hosts a state-carrying and a stateless role of each workgroup
 #endif
+#ifndef GC_QXOR
+#define GC_QXOR 2  // the roles of an API step workgroup's second quad: SIMD s holds roles s and s ^ GC_QXOR
+#endif
+#define ROLL_QUADS_WG 1  // the rollout (k_env_rollout4<OCC, ROLL_QUADS_WG>): one quad per workgroup, four
+                         // workgroups per CU; launches too short to pay for twice the workgroups keep
+                         // the paired form <OCC, QUADS_WG> (gc_host_env.h roll_quads_wg)
 // The 3-fold window's occupancy in LDS (k_env_rollout4<true>; Q1's, a bit per table slot: 64 B per board).
 // The table is open-addressed with linear probing and entries leave it only all at once (a
 // generation bump), so a board whose home slot is free is not in the window -- its probe would
@@ -2153,8 +2170,8 @@ struct OccQ {
     bool probe;  // the next board, if the move stands, is probed in the table
     bool fast;   // the probe in flight is the init block's line: its header reads as a free slot
 };
-// The two workgroups of a CU (blocks b and b + half: tools/pstamp_probe.py reads each wave's
-// HW_ID) start together on the same SIMDs, and at equal priority the SQ issues the older wave
+// (Two quads per workgroup; one: ROLL_TURNS below.)  The two workgroups of a CU (blocks b and
+// b + half: tools/pstamp_probe.py reads each wave's HW_ID) start together on the same SIMDs, and at equal priority the SQ issues the older wave
 // first -- so block b ran its plies at 4.21 us and block b + half at 5.01 (every CU; same roles on
 // every SIMD), and the launch ended with the later ones.  They take turns instead: for turns of
 // GC_TURN_SHIFT (below) plies one workgroup's roles run one level above the other's (s_setprio 3 /
@@ -2426,17 +2443,45 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
 
 // The quads' LDS (static, shared by the role functions below: a direct reference keeps every
 // access a ds_ instruction)
-__shared__ QuadLds g_quad_lds[QUADS_WG];
+__shared__ QuadLds g_quad_lds[ROLL_QUADS_WG];
+__shared__ QuadLds g_quad_lds2[QUADS_WG];  // (the paired form's: a kernel is charged only the array it names)
+template <int QW>
+__device__ __forceinline__ QuadLds& roll_lds(int qw) {
+    if constexpr (QW == ROLL_QUADS_WG) return g_quad_lds[qw];
+    else return g_quad_lds2[qw];
+}
+
+// Turns among the workgroups that share a CU.  A full chip takes a launch's workgroups round
+// by round, so with QW quads per workgroup block b meets b + wgs / (4 / QW) ... on its CU and
+// the block's part of the launch (half, quarter) is its age there (tools/pstamp_probe.py:
+// every CU, profiles/r08_geometry).  At equal priority the SQ issues the older wave first, so
+// the plies ran 4.18 / 4.28 / 4.40 / 4.54 us by quarter with two groups of two alternating
+// and the launch ended with the youngest.  One quad per workgroup: two of the four are one
+// level up in every turn, by a schedule that favours the young -- with ranks 1-4 by (level,
+// age), the pairs {0,3} 4, {1,2} 4, {1,3} 3, {2,3} 5 of 16 turns give every workgroup the
+// mean rank 2.5 (the oldest is up a quarter of the time, the youngest three quarters):
+// 4.32 / 4.37 / 4.40 / 4.40 us.  A nibble per turn, a bit per place.
+#define ROLL_TURNS 0xCA69C6A9C69AC69Cull
+template <int QW>
+__device__ __forceinline__ int roll_place(int block, int wgs) {
+    const int part = wgs / (4 / QW);  // the workgroups of one round over the chip
+    return (part ? block / part : block) & (4 / QW - 1);
+}
+template <int QW>
+__device__ __forceinline__ bool roll_turn(int place, int turn) {
+    if (QW == 2) return ((place ^ turn) & 1) != 0;  // two workgroups per CU: alternating
+    return ((ROLL_TURNS >> (4 * (turn & 15) + place)) & 1) != 0;
+}
 
 // One role's whole launch (its K plies and its stores), inlined into the kernel's switch on the
 // role: a non-inlined function takes generic pointers -- flat memory instructions, which count
 // in lgkmcnt too, so every barrier's lgkmcnt(0) waited for the window probe in flight.
-template <int RR, bool ST, bool OCC>
+template <int RR, bool ST, bool OCC, int QW>
 __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uint64_t seed, u64* __restrict__ htab,
                                       const uint16_t* __restrict__ racts, const EnvDev::InitCache* __restrict__ icd,
                                       u32 rinfo, int plies, uint64_t* __restrict__ stats, u64* __restrict__ trace,
-                                      int qw, int l, int i) {
-    QuadLds& L = g_quad_lds[qw];
+                                      int qw, int l, int i, int place) {
+    QuadLds& L = roll_lds<QW>(qw);
     const bool live = i < nn;
     const int ii = live ? i : nn - 1;  // dead lanes read a valid board, store nothing
     const PairIO in_io(slab, nn);
@@ -2467,7 +2512,6 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     // is probed in the table
     OccQ oq{RR == 1 && hl_of(s.meta) == 0, RR == 1, true, false};
     QuadPend pend{false, false, 0};  // Q0: the first ply's action is the env's
-    const int wg_half = ((nn + QUAD_BOARDS * QUADS_WG - 1) / (QUAD_BOARDS * QUADS_WG)) >> 1;
 #ifdef GC_PSTAMPS
     const unsigned long long g_pst_entry = pst_entry_where();
     unsigned long long rt1 = 0;
@@ -2486,9 +2530,10 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
         // (GC_WG_FAIR, above: this workgroup's turn one level up)
 #ifndef GC_TURN_SHIFT
 #define GC_TURN_SHIFT 2  // turns of 4 plies: same box at K = 20, 8 repeats, 13.32 vs 13.01e9 (events
-                         // 4.53 vs 4.66 us per ply; 8-ply turns 13.22); at K = 1 000 level (run_r06v, w)
+                         // 4.53 vs 4.66 us per ply; 8-ply turns 13.22); at K = 1 000 level (run_r06v, w).
+                         // One quad per workgroup, K = 1 000: 17.06 vs 16.87 (2 plies), 16.82e9 (1)
 #endif
-        const bool up = GC_WG_FAIR && ((((int)blockIdx.x >= wg_half) ? 1 : 0) ^ ((p >> GC_TURN_SHIFT) & 1));
+        const bool up = GC_WG_FAIR && roll_turn<QW>(place, p >> GC_TURN_SHIFT);
         o = quad_ply<RR, OCC>(L, C, l, i, live, s, a, d, h, nst, pr, pend, oq, up);
         const int played = a;  // (Q0: resolved at the ply's start; Q1: read after its barrier A)
 #ifdef GC_PSTAMPS
@@ -2547,8 +2592,8 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
 
 // The fused K-ply rollout on quads (k_env_rollout2's contract: same arguments, state, trace
 // and stats).  Q0 writes the next action and draw counter, Q1 the rest, as W0 / W1 there.
-template <bool OCC>
-__global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amdgpu_waves_per_eu(4)))
+template <bool OCC, int QW>
+__global__ void __launch_bounds__(4 * QUAD_BOARDS * QW) __attribute__((amdgpu_waves_per_eu(4)))
     k_env_rollout4(uint8_t* __restrict__ slab, int nn, uint64_t seed, u64* __restrict__ htab,
                    const uint16_t* __restrict__ racts, const EnvDev::InitCache* __restrict__ icd, u32 rinfo,
                    uint64_t* __restrict__ stats, u64* __restrict__ trace) {
@@ -2556,16 +2601,24 @@ __global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amd
     rinfo &= 0x1FFFFu;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int qw = wv >> 2;  // the quad of this wave within the workgroup
-#ifndef GC_QXOR
-#define GC_QXOR 2  // the roles of a workgroup's second quad: SIMD s holds roles s and s ^ GC_QXOR
-#endif
+    const int wgs = (nn + QUAD_BOARDS * QW - 1) / (QUAD_BOARDS * QW);  // (not gridDim: no implicit kernargs)
+    const int place = roll_place<QW>((int)blockIdx.x, wgs);
+    // role = (wave & 3) ^ rot: a permutation of the quad's roles whatever rot is.  One quad per
+    // workgroup: rot = 0 -- the dispatcher starts each workgroup of a CU one SIMD further on
+    // (waves 0-3 on SIMDs 2130, 1302, 3021, 0213: every CU, tools/pstamp_probe.py), so every
+    // SIMD hosts the four roles, one of each workgroup, as it is; rotating by the place as
+    // well undid that (6 of the 16 role-SIMD pairs per CU, 13.7 vs 16.0e9).  Two: the second
+    // quad's waves land on the first's SIMDs, so its roles are rotated by GC_QXOR.
     const int role = (wv & 3) ^ ((qw & 1) ? GC_QXOR : 0);
     const int l = threadIdx.x & (QUAD_BOARDS - 1);
-    const int i = (blockIdx.x * QUADS_WG + qw) * QUAD_BOARDS + l;
+    const int i = (blockIdx.x * QW + qw) * QUAD_BOARDS + l;
     // Issue priority: a SIMD hosts Q0 + Q2 or Q1 + Q3 (of both quads of a workgroup and of the
-    // CU's other workgroup); the state-carrying roles hold the longer chains, so their waves
-    // issue first (same-box A/B: 13.39-13.46 -> 14.21-14.25e9; Q1 alone 13.99-14.17).  Packed
-    // 2-bit priority per role, GC_QPRIO for diagnostic builds.
+    // CU's other workgroup; one quad per workgroup: all four roles); the state-carrying roles
+    // hold the longer chains, so their waves issue first (same-box A/B: 13.39-13.46 ->
+    // 14.21-14.25e9; Q1 alone 13.99-14.17).  Packed 2-bit priority per role, GC_QPRIO for
+    // diagnostic builds.  Re-measured with one quad per workgroup (K = 1 000, two groups of two
+    // alternating: 16.37e9): no role priorities 15.02, Q2 high throughout 16.09, Q1 low 15.45,
+    // no swap for phase 3 16.06 -- the scheme stays.
 #ifndef GC_QPRIO
 #define GC_QPRIO 0x0A  // Q0 2, Q1 2, Q2 0, Q3 0
 #endif
@@ -2576,13 +2629,13 @@ __global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amd
         default: break;
     }
     switch (role) {
-        case 0: quad_run<0, false, OCC>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i); break;
+        case 0: quad_run<0, false, OCC, QW>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i, place); break;
         case 1:
-            if (stats) quad_run<1, true, OCC>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i);
-            else quad_run<1, false, OCC>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i);
+            if (stats) quad_run<1, true, OCC, QW>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i, place);
+            else quad_run<1, false, OCC, QW>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i, place);
             break;
-        case 2: quad_run<2, false, OCC>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i); break;
-        default: quad_run<3, false, OCC>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i); break;
+        case 2: quad_run<2, false, OCC, QW>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i, place); break;
+        default: quad_run<3, false, OCC, QW>(slab, nn, seed, htab, racts, icd, rinfo, plies, stats, trace, qw, l, i, place); break;
     }
     // The completion word: every workgroup, its stores performed (the barrier waits for them),
     // counts itself; the last one bumps the launch count and writes it to host-mapped memory,
@@ -2596,8 +2649,7 @@ __global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amd
         __syncthreads();
         if (threadIdx.x == 0) {
             const u32 prev = __hip_atomic_fetch_add(dw.ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const u32 wgs = (u32)(nn + QUAD_BOARDS * QUADS_WG - 1) / (QUAD_BOARDS * QUADS_WG);  // (not gridDim: no implicit kernargs)
-            if (prev == wgs - 1) {
+            if (prev == (u32)wgs - 1) {
                 __hip_atomic_store(dw.ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const u32 v = __hip_atomic_fetch_add(dw.seq, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
                 __hip_atomic_store(dw.host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3666,7 +3718,7 @@ __global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amd
                     u32 rinfo /* autoreset << 17 | ic.table << 16 | ic.total */) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int qw = wv >> 2;
-    const int role = (wv & 3) ^ ((qw & 1) ? GC_QXOR : 0);  // as k_env_rollout4: every SIMD a stateful + a stateless role
+    const int role = (wv & 3) ^ ((qw & 1) ? GC_QXOR : 0);  // as k_env_rollout4<OCC, QUADS_WG>: every SIMD a stateful + a stateless role
     const int l = threadIdx.x & (QUAD_BOARDS - 1);
     const int i = (blockIdx.x * QUADS_WG + qw) * QUAD_BOARDS + l;
     ApiOut out = *outp;
@@ -4244,7 +4296,7 @@ __global__ void __launch_bounds__(4 * QUAD_BOARDS * QUADS_WG) __attribute__((amd
                        u32 rinfo /* autoreset << 17 | ic.table << 16 | ic.total */) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int qw = wv >> 2;
-    const int role = (wv & 3) ^ ((qw & 1) ? GC_QXOR : 0);  // as k_env_rollout4: every SIMD a stateful + a stateless role
+    const int role = (wv & 3) ^ ((qw & 1) ? GC_QXOR : 0);  // as k_env_rollout4<OCC, QUADS_WG>: every SIMD a stateful + a stateless role
     const int l = threadIdx.x & (QUAD_BOARDS - 1);
     const int i = (blockIdx.x * QUADS_WG + qw) * QUAD_BOARDS + l;
     ApiOut out = *outp;

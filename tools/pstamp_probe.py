@@ -22,7 +22,9 @@ h = P()
 assert L.gc_env_create(0, n, 0x5EED + 3, None, ctypes.byref(h)) == 0
 assert L.gc_env_rollout(h, 1000, None, None, None, None, None) == 0  # steady state
 quad = os.environ.get("PST_QUAD") == "1"  # the quad kernel (k_env_rollout4): 4 waves per 64 boards
-waves = ((n + 127) // 128) * (8 if quad else 4)
+# PST_WG=1: one quad per workgroup, the rollout's geometry for launches of ROLL_SPLIT_MIN_PLIES plies or more
+wg1 = os.environ.get("PST_WG") == "1"
+waves = ((n + 63) // 64) * 4 if quad and wg1 else ((n + 127) // 128) * (8 if quad else 4)
 out = np.zeros(waves * 12, dtype=np.uint64)
 assert L.gc_debug_pstamps(h, plies, out.ctypes.data_as(P)) == 0
 raw = out.reshape(-1, 12)
@@ -40,8 +42,10 @@ print(f"launch anatomy ({plies} plies, us from the first wave's start): last wav
 if quad:  # k_env_rollout4: 8 waves per workgroup, roles (w & 3) ^ 2 * quad
     w = np.arange(waves) % 8
     role = (w & 3) ^ (((w >> 2) & 1) << 1)
-    if os.environ.get("PST_WG") == "1":  # one quad per workgroup (QUADS_WG=1): roles 0-3 in order
-        role = w & 3
+    wpw = 8  # waves per workgroup
+    if wg1:  # four waves per workgroup, role = wave & 3
+        wpw = 4
+        role = np.arange(waves) & 3
     names = ["phase 0", "wait A", "phase 1", "wait B", "phase 2", "wait C", "phase 3", "wait D"]
     roles = (0, 1, 2, 3)
 else:
@@ -67,7 +71,7 @@ if quad:  # where the slow waves run (k_env_rollout4): wave end and per-ply time
     _, cu_inv, cu_cnt = np.unique(cu_key, return_inverse=True, return_counts=True)
     print(f"CUs used {len(cu_cnt)}, waves per CU: " + ", ".join(f"{c}x{k}" for c, k in zip(*np.unique(cu_cnt, return_counts=True))))
     print("end percentiles (us):", " ".join(f"p{q}:{np.percentile(end, q):.1f}" for q in (0, 10, 25, 50, 75, 90, 99, 100)))
-    wg = np.arange(waves) // 8
+    wg = np.arange(waves) // wpw
     wg_end = np.array([end[wg == g].max() for g in range(wg.max() + 1)])
     wg_per = np.array([per[wg == g].mean() for g in range(wg.max() + 1)])
     print("workgroup end percentiles (us):", " ".join(f"p{q}:{np.percentile(wg_end, q):.1f}" for q in (0, 10, 50, 90, 100)))
@@ -79,6 +83,25 @@ if quad:  # where the slow waves run (k_env_rollout4): wave end and per-ply time
     pairs = {}
     for g in range(wg.max() + 1):
         pairs.setdefault(int(cu_key[wg == g][0]), []).append(g)
+    simd = (where >> 7) & 3
+    if wg1:  # four workgroups per CU: which blocks meet, where each wave index lands, how level they run
+        first = np.array([us[wg == g, 0].min() for g in range(wg.max() + 1)])
+        cnt = np.unique([len(a) for a in pairs.values()], return_counts=True)
+        print("workgroups per CU: " + ", ".join(f"{c}x{k}" for c, k in zip(*cnt)))
+        dist = np.unique([tuple(np.diff(sorted(a))) for a in pairs.values() if len(a) == 4], axis=0, return_counts=True)
+        print("block distances within a CU (x CUs):", [(tuple(int(v) for v in t), int(c)) for t, c in zip(*dist)][:8])
+        print("SIMD of wave index 0-3 (rows) x SIMD 0-3 (columns), waves:")
+        for k in range(4):
+            print("   ", [int(((np.arange(waves) & 3) == k)[simd == sdx].sum()) for sdx in range(4)])
+        roles_simd = [len(set(zip(role[cu_key == c].tolist(), simd[cu_key == c].tolist()))) for c in np.unique(cu_key)]
+        print("distinct (role, SIMD) pairs per CU:", dict(zip(*[x.tolist() for x in np.unique(roles_simd, return_counts=True)])))
+        sp = [max(wg_per[x] for x in a) - min(wg_per[x] for x in a) for a in pairs.values() if len(a) == 4]
+        print(f"per-ply us, slowest - fastest workgroup of a CU: mean {np.mean(sp):.3f}, max {np.max(sp):.3f}; "
+              f"by launch quarter: " + " / ".join(f"{wg_per[q * (len(wg_per) // 4):(q + 1) * (len(wg_per) // 4)].mean():.3f}" for q in range(4)))
+        for g in list(pairs.values())[:4]:
+            print("  CU sample:", [(int(x), f"{wg_per[x]:.3f}", f"start {first[x]:.2f}",
+                                   "simds " + "".join(str(int(v)) for v in simd[wg == x])) for x in sorted(g)])
+        sys.exit(0)
     d = [abs(wg_per[a[0]] - wg_per[a[1]]) for a in pairs.values() if len(a) == 2]
     print(f"CUs with two workgroups: {len(d)}; |per-ply difference| mean {np.mean(d):.3f} us, max {np.max(d):.3f}")
     # which of a CU's two workgroups is the slow one: the later-dispatched (higher index, later
@@ -94,7 +117,6 @@ if quad:  # where the slow waves run (k_env_rollout4): wave end and per-ply time
     nwg = wg.max() + 1
     print(f"slow workgroup of a CU: started later in {slow_later} of {len(pairs)}, higher index in {slow_higher}; "
           f"per-ply us by index half: {wg_per[:nwg // 2].mean():.3f} / {wg_per[nwg // 2:].mean():.3f}")
-    simd = (where >> 7) & 3
     for g in list(pairs.values())[:3]:
         print("  CU sample:", [(int(x), f"{wg_per[x]:.3f}", f"start {first[x]:.2f}",
                                "simds " + "".join(str(int(v)) for v in simd[wg == x])) for x in g])
