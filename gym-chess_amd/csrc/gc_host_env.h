@@ -528,10 +528,11 @@ extern "C" int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, 
     if (row_stride < 4100) return fail("row stride below the 4100 move actions");
     if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
     if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0");
-    if (flags & ~1) return fail("flags: bit 0 = greedy");
+    if (flags & ~3) return fail("flags: bit 0 = greedy, bit 1 = logits relative to the side to move");
     SRV_QUIESCE(e);
     HIPCHK(hipSetDevice(e->device));
     PolicyArgs a;
+    a.meta = e->d.st.meta;
     a.logits = d_logits;
     a.row_stride = (size_t)row_stride;
     a.mask = d_mask;
@@ -545,9 +546,52 @@ extern "C" int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, 
     a.entropy = d_entropy;
     a.n = e->n;
     const dim3 grid((e->n + POL_TILE - 1) / POL_TILE), block(64 * POL_WAVES);
-    if (dtype == 0) k_sample_policy<0><<<grid, block, 0, e->stream>>>(a);
-    else if (dtype == 1) k_sample_policy<1><<<grid, block, 0, e->stream>>>(a);
-    else k_sample_policy<2><<<grid, block, 0, e->stream>>>(a);
+    const bool rel = (flags & 2) != 0;  // logits relative to the side to move
+    if (dtype == 0) { if (rel) k_sample_policy<0, true><<<grid, block, 0, e->stream>>>(a); else k_sample_policy<0, false><<<grid, block, 0, e->stream>>>(a); }
+    else if (dtype == 1) { if (rel) k_sample_policy<1, true><<<grid, block, 0, e->stream>>>(a); else k_sample_policy<1, false><<<grid, block, 0, e->stream>>>(a); }
+    else { if (rel) k_sample_policy<2, true><<<grid, block, 0, e->stream>>>(a); else k_sample_policy<2, false><<<grid, block, 0, e->stream>>>(a); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The network's input planes of every board's current state (gc_planes.h), asynchronous on the
+// env's stream: after a gc_env_step_device2 it describes what that call's mask / obs / pick do.
+// Reads the slab and the 3-fold tables, writes nothing but d_planes.
+template <int DT, bool NHWC>
+static void launch_planes(gc_env* e, const PlanesArgs& a, bool nt) {
+    const dim3 grid((e->n + PLN_WAVES - 1) / PLN_WAVES), block(64 * PLN_WAVES);
+    if (nt) k_encode_planes<DT, NHWC, true><<<grid, block, 0, e->stream>>>(a);
+    else k_encode_planes<DT, NHWC, false><<<grid, block, 0, e->stream>>>(a);
+}
+
+extern "C" int gc_env_encode_planes(gc_env* e, void* d_planes, int dtype, int64_t board_stride, int flags) {
+    static_assert(GC_PLANES == PLN_C, "the header's plane count is the kernel's");
+    if (!e || !d_planes) return fail("null argument");
+    if (dtype < 0 || dtype > 2) return fail("dtype: 0 float32, 1 float16, 2 bfloat16");
+    if (flags & ~3) return fail("flags: bit 0 = side-to-move view, bit 1 = channels-last");
+    if (board_stride != 0 && board_stride < PLN_ELEMS) return fail("board stride below the 1536 elements of a board");
+    if (board_stride % 8) return fail("board stride must be a multiple of 8 elements");
+    if ((uintptr_t)d_planes % 16) return fail("the planes buffer must be 16-byte aligned");
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    PlanesArgs a;
+    a.bb = e->d.st.bb;
+    a.meta = e->d.st.meta;
+    a.hgen = e->d.hgen;
+    a.htab = e->d.htab;
+    a.sp = e->d.ic.spill;
+    a.out = d_planes;
+    a.stride = board_stride ? (size_t)board_stride : (size_t)PLN_ELEMS;
+    a.n = e->n;
+    a.hbits = e->d.hbits;
+    a.persp = flags & 1;
+    a.fide = e->rules != 0;
+    const char* ntv = getenv("GC_PLANES_NT");  // A/B (read per call): non-temporal stores
+    const bool nt = ntv ? atoi(ntv) != 0 : PLN_NT_DEFAULT;
+    const bool nhwc = (flags & 2) != 0;
+    if (dtype == 0) { if (nhwc) launch_planes<0, true>(e, a, nt); else launch_planes<0, false>(e, a, nt); }
+    else if (dtype == 1) { if (nhwc) launch_planes<1, true>(e, a, nt); else launch_planes<1, false>(e, a, nt); }
+    else { if (nhwc) launch_planes<2, true>(e, a, nt); else launch_planes<2, false>(e, a, nt); }
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -20,6 +20,9 @@
 //   D  per board: max and NaN flag, sum of exp and of exp * (x - max), then (sampling) a wave
 //      scan for the CDF.  Boards with m <= 64 never leave registers (D1); longer lists walk
 //      their chunks in three passes, gathering each time (D2: rare, and L2-resident).
+// In k_sample_policy<DT, true> (flags bit 1) the row is relative to the side to move: on a board
+// with BLACK to move the logit of action a is read at pol_mirror(a); the actions themselves,
+// their order and the outputs stay absolute.
 // No per-lane loop over the row, no division but the logit's by the temperature, no scratch.
 #pragma once
 #include <hipcub/hipcub.hpp>
@@ -43,6 +46,7 @@ struct PolicyArgs {
     u64 seed;
     u32 draw;
     int greedy;
+    const u32* meta;  // the env's meta words (read by k_sample_policy<DT, true> only)
     uint16_t* action;
     float* logprob;  // may be NULL
     float* entropy;  // may be NULL
@@ -65,6 +69,17 @@ __device__ __forceinline__ float pol_value(u32 raw) {
         return (float)c.h;
     }
     return __uint_as_float(raw << 16);
+}
+
+// Where the logit of action a sits in a row that is relative to the side to move, on a board with
+// BLACK to move: from and to mirrored (sq ^ 56), the castles' colours swapped.  An involution.
+__device__ __forceinline__ u32 pol_mirror(u32 a) { return a < 4096u ? a ^ 0xE38u : 4096u + ((a - 4096u) ^ 2u); }
+// is board i's row mirrored?  (REL = flags bit 1; without it the env's state is not read and the
+// kernel is the absolute one, instruction for instruction)
+template <bool REL>
+__device__ __forceinline__ bool pol_mirrored(const PolicyArgs& A, int i) {
+    if (!REL) return false;
+    return i < A.n && !(A.meta[i] & M_WHITE);
 }
 
 // Wave-wide reductions and scans through rocPRIM's DPP forms (row shifts and broadcasts in the
@@ -118,7 +133,7 @@ __device__ __forceinline__ u32 pol_kth_action(const u64* row, const uint16_t* in
     return f * 64u + pos;
 }
 
-template <int DT>
+template <int DT, bool REL>
 __global__ __launch_bounds__(64 * POL_WAVES) void k_sample_policy(const PolicyArgs A) {
     __shared__ u64 tile[POL_TILE * POL_ROWS];
     __shared__ uint16_t incl[POL_TILE * (POL_ROWS + 1)];
@@ -166,7 +181,8 @@ __global__ __launch_bounds__(64 * POL_WAVES) void k_sample_policy(const PolicyAr
         const bool on = (u32)lane < m;
         const u32 a = pol_kth_action(tile + b * POL_ROWS, incl + b * (POL_ROWS + 1), on ? (u32)lane : 0u);
         act0[j] = a;
-        raw0[j] = pol_load<DT>(A.logits, on ? (size_t)(base + b) * A.row_stride + a : (size_t)0);
+        const u32 at = pol_mirrored<REL>(A, base + b) ? pol_mirror(a) : a;
+        raw0[j] = pol_load<DT>(A.logits, on ? (size_t)(base + b) * A.row_stride + at : (size_t)0);
     }
 
     // D1: the boards whose list fits one chunk (m <= 64), out of the registers loaded above
@@ -225,12 +241,13 @@ __global__ __launch_bounds__(64 * POL_WAVES) void k_sample_policy(const PolicyAr
         if (i >= A.n || m <= 64) continue;
         const u32 chunks = (m + 63) >> 6;
         const size_t rbase = (size_t)i * A.row_stride;
+        const bool mir = pol_mirrored<REL>(A, i);
         // chunk c: the lane's action and x = logit / T (-inf on idle lanes)
         auto fetch = [&](u32 c, u32& a, float& x) {
             const u32 k = c * 64 + lane;
             const bool on = k < m;
             a = pol_kth_action(row, inc, on ? k : 0u);
-            const u32 raw = pol_load<DT>(A.logits, on ? rbase + a : (size_t)0);
+            const u32 raw = pol_load<DT>(A.logits, on ? rbase + (mir ? pol_mirror(a) : a) : (size_t)0);
             x = on ? pol_value<DT>(raw) / A.temperature : ninf;
         };
         uint16_t out_a = (uint16_t)POL_NONE;

@@ -4650,6 +4650,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
     e.reason[i] = (uint8_t)o.reason;
 }
 
+#include "gc_planes.h"
 
 // ----------------------------------------------------------------------------- host side (the C ABI)
 #include "gc_fen.h"

@@ -302,7 +302,7 @@ class BatchedChessEnv:
     POLICY_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
 
     def sample_policy(self, io, logits, dtype="float32", row_stride=4100, temperature=1.0, seed=None, draw=0,
-                      greedy=False, action=None):
+                      greedy=False, action=None, relative=False):
         """Actions for the positions io.mask describes, from a network's logits on the device
         (gc_env_sample_policy): per board one sample of softmax(logits / temperature) over its
         legal actions (greedy: the argmax), asynchronous on the env's stream.
@@ -311,7 +311,11 @@ class BatchedChessEnv:
         of action a (0..4099).  seed: None = the env's; draw: a counter the caller advances per
         call (same seed and draw = same uniforms).  action: a device pointer to uint16[N], None =
         io's pick buffer, which step_device(io) then plays.  With device_io(policy=True) the
-        log-probs and entropies land in io's logprob / entropy buffers."""
+        log-probs and entropies land in io's logprob / entropy buffers.
+        relative: the logits are in the side-to-move view of encode_planes(perspective=True) --
+        on boards with BLACK to move the logit of action a is read at its mirror image (from and
+        to ^ 56, castle colours swapped); the actions written stay absolute.  The side to move
+        is the env's, so io.mask must describe the env's current state."""
         if dtype not in self.POLICY_DTYPES:
             raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
         p = io.ptr
@@ -323,8 +327,39 @@ class BatchedChessEnv:
         _lib.check(self._L.gc_env_sample_policy(self._h, int(logits), self.POLICY_DTYPES[dtype], int(row_stride),
                                                 p["mask"], io.mask_stride, float(temperature),
                                                 ctypes.c_uint64(self.seed if seed is None else int(seed)),
-                                                int(draw) & 0xFFFFFFFF, int(bool(greedy)), a, p.get("logprob"),
+                                                int(draw) & 0xFFFFFFFF, int(bool(greedy)) | (2 if relative else 0), a,
+                                                p.get("logprob"),
                                                 p.get("entropy")))
+
+    # ------------------------------------------------------------------ network input planes
+    PLANES = 24
+    PLANES_LAYOUTS = {"nchw": 0, "nhwc": 2}
+
+    def planes_buffer(self, dtype="float16", layout="nchw", board_stride=None):
+        """device memory for encode_planes: [N][board_stride] elements of `dtype` (None = 24 * 64)"""
+        return PlanesBuffer(self, dtype=dtype, layout=layout, board_stride=board_stride)
+
+    def encode_planes(self, out, dtype=None, layout=None, perspective=False, board_stride=None):
+        """The network's input for the env's current states (gc_env_encode_planes): 24 planes of
+        8x8 per board -- pieces of both sides, side to move, castle rights, check flags,
+        move_count / 256, the 3-fold counts of the current board, the FIDE en-passant square,
+        ones -- asynchronous on the env's stream.  out: a planes_buffer() (dtype, layout and
+        stride default to the buffer's) or a device pointer (int, e.g. a torch tensor's
+        data_ptr(); defaults float16, "nchw", 24 * 64).  layout "nchw" = [N,24,8,8], "nhwc" =
+        [N,8,8,24].  perspective: the side-to-move view (the side to move comes first, and boards
+        with BLACK to move are mirrored top to bottom); sample_policy(relative=True) reads a
+        policy head's logits in the same view."""
+        buf = out if isinstance(out, PlanesBuffer) else None
+        dtype = dtype if dtype is not None else (buf.dtype if buf else "float16")
+        layout = layout if layout is not None else (buf.layout if buf else "nchw")
+        if board_stride is None:
+            board_stride = buf.board_stride if buf else 0
+        if dtype not in self.POLICY_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
+        if layout not in self.PLANES_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
+        _lib.check(self._L.gc_env_encode_planes(self._h, buf.ptr if buf else int(out), self.POLICY_DTYPES[dtype],
+                                                int(board_stride), self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
 
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""
@@ -384,6 +419,54 @@ class TraceBuffer:
         if w.size:
             _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(w), self.ptr, ctypes.c_uint64(w.nbytes), 2))
         return w
+
+    def close(self):
+        if self.ptr:
+            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(self.ptr))
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlanesBuffer:
+    """Device memory of encode_planes' output: [N][board_stride] raw elements of `dtype`
+    (board_stride >= 24 * 64 elements, a multiple of 8)."""
+
+    _RAW = {"float32": np.float32, "float16": np.uint16, "bfloat16": np.uint16}
+
+    def __init__(self, env, dtype="float16", layout="nchw", board_stride=None):
+        if dtype not in self._RAW:
+            raise ValueError(f"dtype must be one of {sorted(self._RAW)}, got {dtype!r}")
+        if layout not in env.PLANES_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(env.PLANES_LAYOUTS)}, got {layout!r}")
+        self.env, self.dtype, self.layout = env, dtype, layout
+        self.board_stride = int(env.PLANES * 64 if board_stride is None else board_stride)
+        if self.board_stride < env.PLANES * 64 or self.board_stride % 8:
+            raise ValueError(f"board_stride {self.board_stride}: at least {env.PLANES * 64}, a multiple of 8")
+        self.nbytes = env.num_boards * self.board_stride * np.dtype(self._RAW[dtype]).itemsize
+        v = ctypes.c_void_p()
+        _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self.nbytes), ctypes.byref(v)))
+        self.ptr = v.value
+
+    def raw(self):
+        """host copy of the raw elements, [N][board_stride] (float32, or uint16 bit patterns)"""
+        a = np.zeros((self.env.num_boards, self.board_stride), dtype=self._RAW[self.dtype])
+        _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr, ctypes.c_uint64(a.nbytes), 2))
+        return a
+
+    def fetch(self):
+        """host copy decoded to float32: [N,24,8,8] ("nchw") or [N,8,8,24] ("nhwc")"""
+        a = self.raw()[:, : self.env.PLANES * 64]
+        if self.dtype == "float16":
+            a = a.view(np.float16).astype(np.float32)
+        elif self.dtype == "bfloat16":
+            a = (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
+        shape = (24, 8, 8) if self.layout == "nchw" else (8, 8, 24)
+        return np.ascontiguousarray(a).reshape((self.env.num_boards,) + shape)
 
     def close(self):
         if self.ptr:

@@ -188,11 +188,43 @@ int gc_env_step_device2(gc_env* e, const uint16_t* d_actions, int32_t* d_reward,
  * whatever they hold.  Any mask works (0..4100 bits), any n.  Asynchronous on the env's stream:
  * a following gc_env_step_device2 may take d_action as its d_actions.  Fails on a NULL logits /
  * mask / action, an unknown dtype, row_stride < 4100, 0 < mask_stride < n, a temperature that
- * is not finite or <= 0.  Either rule set, either opponent mode (only the mask is read). */
+ * is not finite or <= 0, flag bits above 1.  Either rule set, either opponent mode (only the
+ * mask is read).
+ * flags bit 1: the logits are RELATIVE to the side to move (the view of gc_env_encode_planes
+ * flags bit 0).  On a board whose env state has BLACK to move the logit of legal action a is
+ * read at element mirror(a): a ^ 0xE38 for a < 4096 (from and to each ^ 56), 4096 <-> 4098 and
+ * 4097 <-> 4099 for the castles.  Nothing else changes: the legal actions keep their absolute
+ * action-id order (CDF, greedy ties), d_action is the absolute action gc_env_step_device2 takes,
+ * log-prob and entropy are over the logits as read.  The side to move comes from the env, so
+ * the mask must describe the env's CURRENT state (the mask of its last step, or
+ * gc_env_legal_mask's, uploaded).  With bit 1 clear the env's state is not read. */
 int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
                          const uint64_t* d_mask, int64_t mask_stride, float temperature,
                          uint64_t seed, uint32_t draw, int flags,
                          uint16_t* d_action, float* d_logprob, float* d_entropy);
+/* The network's input: the env's CURRENT state of every board as GC_PLANES planes of 8x8,
+ * written once by one store-bound kernel, asynchronous on the env's stream (after a
+ * gc_env_step_device2 with auto-reset it describes what that call's mask / obs / pick describe).
+ * dtype as gc_env_sample_policy (0 float32, 1 float16, 2 bfloat16); every value is exactly 0, 1
+ * or k/256.  board_stride: elements between boards, 0 = 24 * 64; a multiple of 8, and d_planes
+ * 16-byte aligned.  Layout: element (i, c, sq) at i * board_stride + c * 64 + sq (NCHW), or with
+ * flags bit 1 (channels-last) element (i, sq, c) at i * board_stride + sq * 24 + c; sq = row * 8
+ * + col.  "First" side = WHITE, "second" = BLACK; with flags bit 0 (side-to-move view) "first"
+ * is the side to move and on boards with BLACK to move every square is mirrored, sq -> sq ^ 56.
+ *   0-5    first side's K, Q, R, B, N, P          6-11  second side's
+ *   12     ones iff WHITE is to move (both views)
+ *   13,14  first side's king- / queen-side *_castle_is_possible    15,16  second side's
+ *   17,18  first / second side's *_king_is_checked
+ *   19     move_count / 256 on every square
+ *   20,21  ones iff the current board already occurs in its live 3-fold window with count >= 1 /
+ *          >= 2 (then any move from here is the third occurrence); a read-only find, so
+ *          trajectories with and without this call are identical
+ *   22     rules FIDE: a 1 on the en-passant target square (mirrored like the pieces); else zeros
+ *   23     ones
+ * Either rule set, either opponent mode.  Fails on a NULL env / buffer, an unknown dtype or flag
+ * bit, 0 < board_stride < 1536, a stride that is no multiple of 8, a misaligned buffer. */
+#define GC_PLANES 24
+int gc_env_encode_planes(gc_env* e, void* d_planes, int dtype, int64_t board_stride, int flags);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
