@@ -188,6 +188,33 @@ GC_HD int rep_commit(H& h, const Pos& s, const RepProbe& pr, u32& hl, bool irrev
     return 1;
 }
 
+// Cloning a window into another board's table (gc_clone.h): an entry that is live under the
+// source's generation is the same entry -- tag and count -- under the destination's; any other
+// entry is not part of the window.  Returns whether `hdr` is live; *out = the header to write.
+GC_HD bool rep_clone_hdr(u64 hdr, u32 src_gen, u32 dst_gen, u64* out) {
+    if ((u32)hdr != src_gen) return false;
+    *out = (hdr & ~0xFFFFFFFFull) | (u64)dst_gen;
+    return true;
+}
+
+// The whole window of `src` into `dst` (tables of the same size), entry by entry: the
+// destination's generation is bumped once, which kills every entry it held, and each live source
+// entry lands at its own slot position -- a position depends on the board's key and the table
+// size alone, so probe chains survive.  Returns the entries copied (the window's length).
+template <class HS, class HD>
+GC_HD int rep_clone_table(const HS& src, HD& dst) {
+    dst.bump_gen();
+    const u32 sg = src.gen(), dg = dst.gen();
+    int n = 0;
+    for (int pos = 0; pos < (1 << src.bits()); pos++) {
+        RepEntry e = src.load(pos);
+        if (!rep_clone_hdr(e.hdr, sg, dg, &e.hdr)) continue;
+        dst.store(pos, e);
+        n++;
+    }
+    return n;
+}
+
 // One player_move (chess_v2.py:393-420) of the legal `action` of the side to move, with the
 // engine's update_state and the next side's move list: on return 0, `s` is the new position
 // (check flags, window length, M_DONE if the PRE-move board reached 3 occurrences) and

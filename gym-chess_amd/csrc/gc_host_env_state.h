@@ -36,6 +36,10 @@ struct gc_env {
     hipStream_t sub[GC_MAX_SUBSTREAMS] = {};
     hipEvent_t sub_ev[GC_MAX_SUBSTREAMS] = {};
     hipEvent_t fork_ev = nullptr;
+    // gc_env_clone_boards: the event that orders a clone between this env's stream and the other
+    // env's, and the count of pairs skipped for an index out of range (device, since creation)
+    hipEvent_t clone_ev = nullptr;
+    unsigned long long* clone_skipped = nullptr;
     // the spill table of a BLACK agent's windows (gc_env.h; SpillTab): its slot counters are
     // copied to pinned host memory after every stepping call and checked before the next one
     int sp_bits = 0;
@@ -62,7 +66,7 @@ struct gc_env {
 
 static void env_free(gc_env* e) {
     void* ps[] = {e->api_out, e->reset_acts, e->icd, e->icd_f, e->racts_f, e->open_cache, e->open_acts, e->ep, e->slab, e->d.htab, e->mbox, e->m8, e->mask,
-                  e->list, e->counts, e->lmask, e->stats};
+                  e->list, e->counts, e->lmask, e->stats, e->clone_skipped};
     for (void* p : ps) if (p) (void)hipFree(p);
     for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);
     for (int j = 0; j < GC_MAX_SUBSTREAMS; j++) {
@@ -70,6 +74,7 @@ static void env_free(gc_env* e) {
         if (e->sub[j]) (void)hipStreamDestroy(e->sub[j]);
     }
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
+    if (e->clone_ev) (void)hipEventDestroy(e->clone_ev);
     if (e->d.ic.spill.ent) (void)hipFree(e->d.ic.spill.ent);
     if (e->d.ic.spill.ctr) (void)hipFree(e->d.ic.spill.ctr);
     if (e->sp_ctr_h) (void)hipHostFree(e->sp_ctr_h);

@@ -4651,6 +4651,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 }
 
 #include "gc_planes.h"
+#include "gc_clone.h"
 
 // ----------------------------------------------------------------------------- host side (the C ABI)
 #include "gc_fen.h"
@@ -4660,4 +4661,5 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_host_env_state.h"
 #include "gc_host_spill.h"
 #include "gc_host_env.h"
+#include "gc_host_clone.h"
 #include "gc_host_ckpt.h"

@@ -86,6 +86,8 @@ SIGNATURES = {
     "gc_env_sample_policy": (_I, [_P, _P, _I, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, _U64,
                                   ctypes.c_uint32, _I, _P, _P, _P]),
     "gc_env_encode_planes": (_I, [_P, _P, _I, ctypes.c_int64, _I]),
+    "gc_env_clone_boards": (_I, [_P, _P, _P, _P, _I]),
+    "gc_env_clone_errors": (_I, [_P, _P]),
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),
     "gc_device_free": (_I, [_I, _P]),

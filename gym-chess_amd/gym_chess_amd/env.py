@@ -57,6 +57,7 @@ class BatchedChessEnv:
 
     def close(self):
         if getattr(self, "_h", None):
+            self._clone_free()
             self._L.gc_env_destroy(self._h)
             self._h = None
 
@@ -360,6 +361,65 @@ class BatchedChessEnv:
             raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
         _lib.check(self._L.gc_env_encode_planes(self._h, buf.ptr if buf else int(out), self.POLICY_DTYPES[dtype],
                                                 int(board_stride), self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
+
+    # ------------------------------------------------------------------ board clones (search)
+    def clone_boards(self, src, src_idx, dst_idx, count=None):
+        """Boards dst_idx[j] of this env become copies of boards src_idx[j] of `src` (a
+        BatchedChessEnv; self is allowed) on the device (gc_env_clone_boards): position, flags,
+        move_count, done / reward / reason and the live 3-fold window, so the copies continue
+        exactly as their sources would; this env's policy streams and step counters stay.  One
+        launch on this env's stream, ordered after src's earlier work.
+        src_idx / dst_idx: array-likes of equal length -- converted to int32 and uploaded to a
+        staging buffer of this env on its stream (the upload is a synchronous copy, so it waits
+        for the stream's earlier work; the clone itself does not) -- or device pointers (ints) to
+        int32[count], which make the whole call asynchronous.  Destination indices must be
+        distinct, and with src is self no board may be both a source and a destination; a pair
+        with an index out of range is skipped and counted (clone_errors).  Not for player_color
+        BLACK envs (checkpoint / load)."""
+        if not isinstance(src, BatchedChessEnv):
+            raise TypeError("src must be a BatchedChessEnv")
+        if isinstance(src_idx, int) and isinstance(dst_idx, int):
+            if count is None:
+                raise ValueError("device pointers need count")
+            m, ps, pd = int(count), src_idx or None, dst_idx or None
+        else:
+            s = np.ascontiguousarray(src_idx, dtype=np.int32).reshape(-1)
+            d = np.ascontiguousarray(dst_idx, dtype=np.int32).reshape(-1)
+            if s.size != d.size:
+                raise ValueError(f"src_idx holds {s.size} indices, dst_idx {d.size}")
+            if count is not None and int(count) != s.size:
+                raise ValueError(f"count {count} != the arrays' length {s.size}")
+            m = int(s.size)
+            ps = pd = None
+            if m:
+                ps = self._clone_staging(m)
+                pd = ps + 4 * self._clone_cap
+                for p, a in ((ps, s), (pd, d)):  # on the env's stream: after the previous clone read them
+                    _lib.check(self._L.gc_env_copy(self._h, p, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+        _lib.check(self._L.gc_env_clone_boards(self._h, src._h, ps, pd, m))
+
+    def _clone_staging(self, m):
+        """device int32[2][cap] for clone_boards' uploaded indices, grown by doubling"""
+        if m > getattr(self, "_clone_cap", 0):
+            self._clone_free()  # (gc_device_free waits for the device: no clone still reads it)
+            cap = max(256, 1 << (m - 1).bit_length())
+            v = ctypes.c_void_p()
+            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(8 * cap), ctypes.byref(v)))
+            self._clone_buf, self._clone_cap = v.value, cap
+        return self._clone_buf
+
+    def _clone_free(self):
+        if getattr(self, "_clone_buf", None):
+            self.synchronize()
+            self._L.gc_device_free(self.device, ctypes.c_void_p(self._clone_buf))
+        self._clone_buf, self._clone_cap = None, 0
+
+    def clone_errors(self):
+        """pairs clone_boards skipped into this env since its creation (an index out of range);
+        waits for the env's stream"""
+        v = ctypes.c_uint64()
+        _lib.check(self._L.gc_env_clone_errors(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""

@@ -161,7 +161,8 @@ int gc_env_step(gc_env* e, const uint16_t* actions, int32_t* reward, uint8_t* do
  * d_pick[n] (a uniform Philox pick over the new list, the k-th legal action in action-id
  * order -- the mask's order; also the env's next policy action).  flags bit 0: auto-reset finished boards (the mask / obs / pick then describe
  * the new episode).  Asynchronous on the env's stream: order your own work with it through
- * gc_env_get_stream (a hipStream_t) or gc_env_synchronize.  Reference rules only. */
+ * gc_env_get_stream (a hipStream_t) or gc_env_synchronize.  Either rule set (gc_env_set_rules),
+ * either opponent mode. */
 int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, uint8_t* d_done,
                        uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
                        uint16_t* d_pick, int flags);
@@ -225,6 +226,38 @@ int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row
  * bit, 0 < board_stride < 1536, a stride that is no multiple of 8, a misaligned buffer. */
 #define GC_PLANES 24
 int gc_env_encode_planes(gc_env* e, void* d_planes, int dtype, int64_t board_stride, int flags);
+/* Boards copied on the device, for a search that keeps one env state per tree node: for every
+ * j < m, board d_dst_idx[j] of `dst` becomes a copy of board d_src_idx[j] of `src` (src == dst
+ * is allowed).  Both index arrays are DEVICE memory of m int32.  One launch, asynchronous on
+ * dst's stream, no host synchronisation: with src != dst it runs after the work already on src's
+ * stream, and src's later work runs after it (events).
+ * Copied: the 7 bitboards; the meta word (side to move, castle rights, check flags, done,
+ * move_count, the 3-fold window's length, the FIDE en-passant file); the last step's reward /
+ * done / reason; and every live entry of the source's 3-fold window with its count.  Kept on the
+ * destination: its policy draw counter, its step counter and its board index -- so its policy /
+ * random-opponent stream stays its own, and random replies after a clone differ from the
+ * source's.  The env's policy actions become stale (as after gc_env_set_states): call
+ * gc_env_select_random before gc_env_step_random / gc_env_rollout.
+ * Window: the destination's generation is bumped once, so every entry its table held is dead;
+ * each entry that is live under the source's generation is written to the same slot position of
+ * the destination's table with the destination's new generation, tag and count unchanged.  Slot
+ * positions depend only on the board's key and the table size, so probe chains survive -- which
+ * is why both envs need tables of the same size.  Afterwards the destination continues under any
+ * action sequence exactly as the source would: same rewards, done, reasons, masks, observations,
+ * counts, the 3-fold verdict at the same step, the same gc_env_encode_planes output.
+ * The caller guarantees that the destination indices are distinct and, with src == dst, that no
+ * board is both a source and a destination of one call; the boards involved in a violation end
+ * in an unspecified state.  Whatever the arrays hold, every access stays in bounds: a pair with
+ * either index out of range is skipped and counted (gc_env_clone_errors).
+ * Fails (nothing launched) on a NULL env, m < 0, a NULL array with m > 0, envs on different
+ * devices, under different rules or with 3-fold tables of different sizes, and when either env
+ * is a player_color BLACK env: its windows can live partly in the env's shared spill table,
+ * which a position-for-position copy does not cover -- gc_env_save / gc_env_load remain the
+ * route there.  m == 0 succeeds and does nothing. */
+int gc_env_clone_boards(gc_env* dst, gc_env* src, const int32_t* d_src_idx, const int32_t* d_dst_idx, int m);
+/* the pairs gc_env_clone_boards skipped into `dst` since its creation (an index out of range);
+ * synchronises dst's stream */
+int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
