@@ -151,10 +151,18 @@ GC_HD void rep_prefetch(H& h, const Pos& s, RepProbe& pr) {
     pr.e0 = h.load((int)(pr.key & ((1u << h.bits()) - 1)));
 }
 
+// rep_commit's default knowledge of the slots beyond the home slot: none, every one is loaded
+struct RepNoneFree {
+    GC_HDM bool operator()(u32) const { return false; }
+};
+
 // Returns how many times the board has been the pre-move board so far, this one included;
 // 0 if it is new and the window is full (hist_cap).
-template <class H>
-GC_HD int rep_commit(H& h, const Pos& s, const RepProbe& pr, u32& hl, bool irrev) {
+// known_free(pos), asked for every slot probed beyond the home slot: true only if the caller
+// knows that slot pos holds no entry of this generation -- the slot is then not loaded, and the
+// probe ends there as it would after loading it (the fused rollout's occupancy bitmap).
+template <class H, class KF = RepNoneFree>
+GC_HD int rep_commit(H& h, const Pos& s, const RepProbe& pr, u32& hl, bool irrev, KF known_free = KF{}) {
     const int bits = h.bits();
     const u32 size_mask = (1u << bits) - 1;
     u32 gen = h.gen();
@@ -162,7 +170,10 @@ GC_HD int rep_commit(H& h, const Pos& s, const RepProbe& pr, u32& hl, bool irrev
     int c = 0;
     RepEntry e = pr.e0;
     for (int probe = 0; probe <= (int)size_mask; probe++) {
-        if (probe) e = h.load((int)pos);
+        if (probe) {
+            if (known_free(pos)) break;
+            e = h.load((int)pos);
+        }
         if ((u32)e.hdr != gen) break;  // free for this generation
         if ((u32)((e.hdr >> 32) & tag_mask(bits)) == tag && rep_same(e, s)) {
             c = (int)(e.hdr >> 56) + 1;

@@ -64,8 +64,30 @@ __device__ __forceinline__ void gc_pst_mark(int k) {
     __builtin_amdgcn_sched_barrier(0);
 }
 #define PST(k) gc_pst_mark(k)
+// the quad rollout's Q1, phase 2, split by whether any lane of the wave loaded a window slot
+// beyond its home slot in this ply (rep_commit's in-loop load): per wave, the plies that did
+// and the cycles of their phase 2
+__shared__ unsigned long long gc_pst_run[8][2];
+__device__ unsigned long long* g_pst_run_out;
+__device__ __forceinline__ void gc_pst_mark_run(int k, bool loaded) {
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long t = __builtin_amdgcn_s_memtime();
+    const bool any = __any(loaded);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        gc_pst[w][k] += t - gc_pst[w][8];
+        if (any) {
+            gc_pst_run[w][0] += 1;
+            gc_pst_run[w][1] += t - gc_pst[w][8];
+        }
+        gc_pst[w][8] = t;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+#define PST_LOADED(x) do { if (x) pst_loaded = true; } while (0)
 #else
 #define PST(k)
+#define PST_LOADED(x)
 #endif
 #include "gc_core.h"
 #include "gc_env.h"
@@ -2181,6 +2203,9 @@ struct OccQ {
 #ifndef GC_WG_FAIR
 #define GC_WG_FAIR 1  // 0: A/B
 #endif
+#ifndef GC_OCC_RUN
+#define GC_OCC_RUN 1  // the commit's probes beyond the home slot consult the bitmap (0: A/B, every one loaded)
+#endif
 // s_setprio(x), one level up on the plies where this workgroup has its turn (GC_WG_FAIR)
 #define QSETPRIO(x, up)                                       \
     do {                                                      \
@@ -2192,6 +2217,9 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
                                             u32& d, DevHist& h, u32& nst, RepProbe& pr, QuadPend& pend, OccQ& oq,
                                             bool up = false) {
     constexpr bool CARRY = R < 2;  // Q0 / Q1 hold the state
+#ifdef GC_PSTAMPS
+    bool pst_loaded = false;  // Q1: the commit loaded a slot beyond the home slot
+#endif
     // Q2's pick (phase 3's longest) is raised over Q0's outcome there: 14.43-14.63 -> 14.90-15.12e9
     if (R == 0) QSETPRIO(2, up);
     if (R == 2) QSETPRIO(0, up);
@@ -2321,7 +2349,24 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
             pin(pr.e0.hdr); pin(pr.e0.k); pin(pr.e0.q); pin(pr.e0.r);
             pin(pr.e0.b); pin(pr.e0.n); pin(pr.e0.p); pin(pr.e0.w);
             if (OCC && oq.fast) pr.e0.hdr = (u64)(h.gen() ^ 1u);  // (after the wait: no loaded register merged)
-            c = rep_commit(h, s, pr, hl, irrev);  // table write deferred to h.commit()
+            // table write deferred to h.commit()
+            if constexpr (OCC && GC_OCC_RUN) {
+                // Beyond a taken home slot the bitmap answers for the table as well: a slot whose
+                // bit is clear holds no entry of this window, so the probe ends there unloaded --
+                // in nine of ten such plies that is slot home + 1, and the load was a memory round
+                // trip on this phase's chain.  Read here, not carried from phase 1: the bitmap
+                // holds every entry up to the last ply's (this ply's is added below).
+                c = rep_commit(h, s, pr, hl, irrev, [&](u32 pos) {
+                    const bool free = oq.valid && ((L.occ[pos >> 6][l] >> (pos & 63)) & 1) == 0;
+                    PST_LOADED(!free);
+                    return free;
+                });
+            } else {  // every slot loaded (the stamp build counts the plies that do)
+                c = rep_commit(h, s, pr, hl, irrev, [&](u32) {
+                    PST_LOADED(true);
+                    return false;
+                });
+            }
             if (!OCC) {
             } else if (irrev) {  // the window is cleared: from the next ply on the bitmap mirrors it again
                 oq.valid = true;
@@ -2352,6 +2397,10 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         for (int k = 0; k < 4; k++) L.cwx[1][k][l] = Q.cw[k];
     }
     if (R == 0) L.part[0][l] = (u32)Q.part;
+#ifdef GC_PSTAMPS
+    if (R == 1) gc_pst_mark_run(4, pst_loaded);
+    else
+#endif
     PST(4);
     pair_barrier();
     PST(5);
@@ -2517,6 +2566,7 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     unsigned long long rt1 = 0;
     if (l == 0) {
         for (int k = 0; k < 8; k++) gc_pst[threadIdx.x >> 6][k] = 0;
+        gc_pst_run[threadIdx.x >> 6][0] = gc_pst_run[threadIdx.x >> 6][1] = 0;
         gc_pst[threadIdx.x >> 6][8] = __builtin_amdgcn_s_memtime();
     }
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
@@ -2564,6 +2614,10 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
         g_pst_out[w * 12 + 9] = rt0;
         g_pst_out[w * 12 + 10] = rt1;
         g_pst_out[w * 12 + 11] = __builtin_amdgcn_s_memrealtime();
+        if (g_pst_run_out != nullptr) {
+            g_pst_run_out[w * 2] = gc_pst_run[threadIdx.x >> 6][0];
+            g_pst_run_out[w * 2 + 1] = gc_pst_run[threadIdx.x >> 6][1];
+        }
     }
 #endif
     if (!live || RR >= 2) return;

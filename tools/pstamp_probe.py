@@ -2,7 +2,10 @@
 k_env_rollout2<false, 0> (phase work and barrier waits, s_memtime), summed over a launch of
 --plies plies and averaged per ply over the waves (build: tools/build_variants.sh pst
 "-DGC_PSTAMPS" -> tools/_lib_pst.so).  Segments: phase 0 | wait A | phase 1 | wait B |
-phase 2 | wait C | phase 3 (outcome, pick / commit) | wait D (next action to W1)."""
+phase 2 | wait C | phase 3 (outcome, pick / commit) | wait D (next action to W1).  The quad
+rollout's Q1 also reports phase 2 by whether a lane of the wave loaded a window slot beyond its
+home slot in that ply (rep_commit's in-loop load; -DGC_OCC_RUN=0 builds the form that loads
+every slot)."""
 import ctypes
 import os
 import sys
@@ -14,7 +17,7 @@ L = ctypes.CDLL(os.environ.get("PST_LIB") or os.path.join(ROOT, "tools", "_lib_p
 P = ctypes.c_void_p
 L.gc_env_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, P, P]
 L.gc_env_rollout.argtypes = [P, ctypes.c_int, P, P, P, P, P]
-L.gc_debug_pstamps.argtypes = [P, ctypes.c_int, P]
+L.gc_debug_pstamps.argtypes = [P, ctypes.c_int, P, P]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 plies = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 pmap = int(os.environ.get("PST_MAP", "2"))
@@ -26,7 +29,8 @@ quad = os.environ.get("PST_QUAD") == "1"  # the quad kernel (k_env_rollout4): 4 
 wg1 = os.environ.get("PST_WG") == "1"
 waves = ((n + 63) // 64) * 4 if quad and wg1 else ((n + 127) // 128) * (8 if quad else 4)
 out = np.zeros(waves * 12, dtype=np.uint64)
-assert L.gc_debug_pstamps(h, plies, out.ctypes.data_as(P)) == 0
+run = np.zeros(waves * 2, dtype=np.uint64)  # the quad rollout's Q1: plies with an in-loop window load, their phase 2
+assert L.gc_debug_pstamps(h, plies, out.ctypes.data_as(P), run.ctypes.data_as(P)) == 0
 raw = out.reshape(-1, 12)
 st = raw[:, :8].astype(np.float64) / plies
 where = (raw[:, 8] >> np.uint64(44)).astype(np.int64)  # placement: cu | sh | se | simd | xcc
@@ -59,6 +63,12 @@ for r in roles:
     print(f"[{'Q' if quad else 'W'}{r}] {len(s)} waves, {tot:.0f} cycles per ply")
     for k in range(len(names)):
         print(f"   {names[k]:>8}: {s[:, k].mean():7.0f}  ({s[:, k].mean() / tot:5.1%})")
+    if quad and r == 1:  # phase 2 by whether a lane of the wave loaded a slot beyond its home slot (rep_commit's loop)
+        rn = run.reshape(-1, 2)[role == 1].astype(np.float64)
+        with_load, p2 = rn[:, 0].sum(), raw[role == 1, 4].astype(np.float64).sum()
+        without = len(rn) * plies - with_load
+        print(f"   phase 2, plies with an in-loop window load: {with_load / (len(rn) * plies):.4f} of wave-plies, "
+              f"{rn[:, 1].sum() / max(with_load, 1):.0f} cycles; without: {(p2 - rn[:, 1].sum()) / max(without, 1):.0f} cycles")
 if quad:  # where the slow waves run (k_env_rollout4): wave end and per-ply time by XCD and by CU
     xcc = where >> 9
     cu_key = where & 0x7F | (xcc << 7)
