@@ -554,6 +554,59 @@ extern "C" int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, 
     return 0;
 }
 
+// Legal-move priors on the device (gc_priors.h): per row every legal action of its board with its
+// prior softmax(logits / T), as a compact [rows][cap] child list for a batched search.  Row j
+// reads logits row j and the mask column of board d_board_idx[j] (NULL: board j).  Reads only
+// the mask, the logits at legal actions and (flags bit 1) the env's side to move; asynchronous on
+// the env's stream.
+template <int DT>
+static void launch_priors(gc_env* e, const PriorsArgs& a, bool rel) {
+    const dim3 grid((unsigned)(((int64_t)a.rows + POL_TILE - 1) / POL_TILE)), block(64 * POL_WAVES);
+    const bool idx = a.board_idx != nullptr;
+    if (rel) { if (idx) k_policy_priors<DT, true, true><<<grid, block, 0, e->stream>>>(a); else k_policy_priors<DT, true, false><<<grid, block, 0, e->stream>>>(a); }
+    else { if (idx) k_policy_priors<DT, false, true><<<grid, block, 0, e->stream>>>(a); else k_policy_priors<DT, false, false><<<grid, block, 0, e->stream>>>(a); }
+}
+
+extern "C" int gc_env_policy_priors(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
+                                    const uint64_t* d_mask, int64_t mask_stride,
+                                    const int32_t* d_board_idx, int rows,
+                                    float temperature, int flags, int cap,
+                                    uint16_t* d_actions, float* d_priors, int32_t* d_count, uint16_t* d_logit_idx) {
+    if (!e || !d_logits || !d_mask || !d_actions || !d_priors) return fail("null argument");
+    if (dtype < 0 || dtype > 2) return fail("dtype: 0 float32, 1 float16, 2 bfloat16");
+    if (row_stride < 4100) return fail("row stride below the 4100 move actions");
+    if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return fail("temperature must be finite and > 0");
+    if (flags & ~2) return fail("flags: bit 1 = logits relative to the side to move; every other bit 0");
+    if (cap < 1 || cap > 4100) return fail("cap must be in [1, 4100]");
+    if (rows < 0) return fail("negative row count");
+    if (!d_board_idx && rows > e->n) return fail("more rows than boards without a board index");
+    if (rows == 0) return 0;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    PriorsArgs a;
+    a.logits = d_logits;
+    a.row_stride = (size_t)row_stride;
+    a.mask = d_mask;
+    a.mask_stride = mask_stride ? (size_t)mask_stride : (size_t)e->n;
+    a.temperature = temperature;
+    a.meta = e->d.st.meta;
+    a.board_idx = d_board_idx;
+    a.rows = rows;
+    a.n = e->n;
+    a.cap = (u32)cap;
+    a.actions = d_actions;
+    a.priors = d_priors;
+    a.count = d_count;
+    a.logit_idx = d_logit_idx;
+    const bool rel = (flags & 2) != 0;  // logits relative to the side to move
+    if (dtype == 0) launch_priors<0>(e, a, rel);
+    else if (dtype == 1) launch_priors<1>(e, a, rel);
+    else launch_priors<2>(e, a, rel);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // The network's input planes of every board's current state (gc_planes.h), asynchronous on the
 // env's stream: after a gc_env_step_device2 it describes what that call's mask / obs / pick do.
 // Reads the slab and the 3-fold tables, writes nothing but d_planes.

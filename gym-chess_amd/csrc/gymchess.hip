@@ -94,6 +94,7 @@ __device__ __forceinline__ void gc_pst_mark_run(int k, bool loaded) {
 #include "gc_perft.h"
 #include "gc_fide.h"
 #include "gc_policy.h"
+#include "gc_priors.h"
 #include "../../include/gymchess.h"
 
 using namespace gc;

@@ -58,6 +58,7 @@ class BatchedChessEnv:
     def close(self):
         if getattr(self, "_h", None):
             self._clone_free()
+            self._priors_free()
             self._L.gc_env_destroy(self._h)
             self._h = None
 
@@ -332,6 +333,72 @@ class BatchedChessEnv:
                                                 p.get("logprob"),
                                                 p.get("entropy")))
 
+    # ------------------------------------------------------------------ legal-move priors (search)
+    def priors_buffer(self, rows, cap=64, logit_index=False):
+        """device memory for policy_priors: actions uint16[rows][cap], priors float32[rows][cap],
+        count int32[rows] and, with logit_index, logit_index uint16[rows][cap]"""
+        return PriorsBuffer(self, rows, cap=cap, logit_index=logit_index)
+
+    def policy_priors(self, io, logits, out, boards=None, rows=None, dtype="float32", row_stride=4100,
+                      temperature=1.0, relative=False):
+        """The expansion step of a batched search (gc_env_policy_priors): per row every legal
+        action of a board with its prior softmax(logits / temperature), in action-id order, as a
+        compact child list in `out` (a priors_buffer()), asynchronous on the env's stream.
+        logits: a device pointer to [rows][row_stride] elements of `dtype`; row j belongs to board
+        boards[j] of io.mask.  boards: None = board j (rows defaults to out.rows); an array-like
+        of board indices -- converted to int32 and uploaded on the env's stream into a staging
+        buffer of this env (a synchronous copy, as clone_boards') --; or a device pointer (int)
+        to int32[rows], with rows.  Duplicates are fine; an index outside [0, N) gives count -1
+        and an all-padding row.  Slots past a row's list hold 0xFFFF / 0.0; count may exceed
+        out.cap, the priors are normalised over all legal actions either way.
+        relative: the logits are in the side-to-move view (sample_policy's flag); the actions
+        stay absolute, and out's logit_index says where each prior's logit was read."""
+        if dtype not in self.POLICY_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
+        if not isinstance(out, PriorsBuffer):
+            raise TypeError("out must be a priors_buffer()")
+        mask = io.ptr.get("mask")
+        if not mask:
+            raise ValueError("no legal mask: allocate io with mask=True")
+        if boards is None:
+            pb, m = None, out.rows if rows is None else int(rows)
+        elif isinstance(boards, int):
+            if rows is None:
+                raise ValueError("a device pointer needs rows")
+            pb, m = boards or None, int(rows)
+        else:
+            b = np.ascontiguousarray(boards, dtype=np.int64).reshape(-1)
+            if rows is not None and int(rows) != b.size:
+                raise ValueError(f"rows {rows} != the board array's length {b.size}")
+            b = np.clip(b, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
+            pb, m = None, int(b.size)
+            if m:
+                pb = self._priors_staging(m)
+                _lib.check(self._L.gc_env_copy(self._h, pb, _lib.ptr(b), ctypes.c_uint64(b.nbytes), 1))
+        if m > out.rows:
+            raise ValueError(f"{m} rows, the priors buffer holds {out.rows}")
+        p = out.ptr
+        _lib.check(self._L.gc_env_policy_priors(self._h, int(logits), self.POLICY_DTYPES[dtype], int(row_stride),
+                                                mask, io.mask_stride, pb, m, float(temperature),
+                                                2 if relative else 0, out.cap, p["actions"], p["priors"], p["count"],
+                                                p.get("logit_index")))
+
+    def _priors_staging(self, m):
+        """device int32[cap] for policy_priors' uploaded board indices, grown by doubling"""
+        if m > getattr(self, "_priors_cap", 0):
+            self._priors_free()  # (gc_device_free waits for the device: no launch still reads it)
+            cap = max(256, 1 << (m - 1).bit_length())
+            v = ctypes.c_void_p()
+            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(4 * cap), ctypes.byref(v)))
+            self._priors_buf, self._priors_cap = v.value, cap
+        return self._priors_buf
+
+    def _priors_free(self):
+        if getattr(self, "_priors_buf", None):
+            self.synchronize()
+            self._L.gc_device_free(self.device, ctypes.c_void_p(self._priors_buf))
+        self._priors_buf, self._priors_cap = None, 0
+
     # ------------------------------------------------------------------ network input planes
     PLANES = 24
     PLANES_LAYOUTS = {"nchw": 0, "nhwc": 2}
@@ -532,6 +599,51 @@ class PlanesBuffer:
         if self.ptr:
             self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(self.ptr))
             self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PriorsBuffer:
+    """Device memory of policy_priors' output: actions uint16[rows][cap], priors float32[rows][cap],
+    count int32[rows] and optionally logit_index uint16[rows][cap] (ptr[...] are device pointers)."""
+
+    _SPEC = {"actions": np.uint16, "priors": np.float32, "count": np.int32, "logit_index": np.uint16}
+
+    def __init__(self, env, rows, cap=64, logit_index=False):
+        self.env, self.rows, self.cap = env, int(rows), int(cap)
+        if self.rows < 0:
+            raise ValueError(f"rows {rows} < 0")
+        if not 1 <= self.cap <= C.N_ACTIONS - 1:
+            raise ValueError(f"cap {cap}: between 1 and {C.N_ACTIONS - 1}")
+        self.ptr = {}
+        for k in ("actions", "priors", "count") + (("logit_index",) if logit_index else ()):
+            v = ctypes.c_void_p()
+            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self._shape(k)[1]), ctypes.byref(v)))
+            self.ptr[k] = v.value
+
+    def _shape(self, k):
+        shape = (self.rows,) if k == "count" else (self.rows, self.cap)
+        return shape, int(np.prod(shape, dtype=np.int64)) * np.dtype(self._SPEC[k]).itemsize
+
+    def fetch(self, *keys):
+        """host copies (waits for the env's stream): dict of [rows][cap] / [rows] arrays"""
+        out = {}
+        for k in keys or self.ptr:
+            shape, nb = self._shape(k)
+            a = np.zeros(shape, dtype=self._SPEC[k])
+            if nb:
+                _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(nb), 2))
+            out[k] = a
+        return out
+
+    def close(self):
+        for v in self.ptr.values():
+            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
+        self.ptr = {}
 
     def __del__(self):
         try:

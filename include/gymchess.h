@@ -203,6 +203,40 @@ int gc_env_sample_policy(gc_env* e, const void* d_logits, int dtype, int64_t row
                          const uint64_t* d_mask, int64_t mask_stride, float temperature,
                          uint64_t seed, uint32_t draw, int flags,
                          uint16_t* d_action, float* d_logprob, float* d_entropy);
+/* Legal-move priors for a batched search (the expansion of a tree node): per row EVERY legal
+ * action of a board with its prior probability, as a compact child list -- the sparse mapping of
+ * gc_env_sample_policy, so no mask is unpacked and no illegal logit is read.
+ * Logits: d_logits row j at element j * row_stride (>= 4100), dtype as gc_env_sample_policy.
+ * Mask: d_mask / mask_stride as gc_env_step_device2 (0 = n).  Row j describes board
+ * d_board_idx[j] (DEVICE int32[rows]), or board j when d_board_idx is NULL (then rows <= n): a
+ * network that ran on a few rows of a tree env passes those rows' boards.  Duplicates are
+ * allowed (only the rows are written); an index outside [0, n) gives count = -1 and an
+ * all-padding row, and nothing is accessed out of bounds.
+ * Outputs, row j at element j * cap: the legal actions a_1 < ... < a_m are the mask's set bits in
+ * action-id order (d_pick's and gc_env_sample_policy's order); d_actions[j][k] = a_(k+1),
+ * d_priors[j][k] = softmax(logit[a] / temperature) of it in fp32, normalised over ALL m, for
+ * k < min(m, cap); slots min(m, cap) .. cap - 1 hold the padding 0xFFFF / 0.0f (/ 0xFFFF), so the
+ * whole [rows][cap] block is defined after the call.  d_count[j] (NULL = skip) = m: it may exceed
+ * cap, and the cap entries written then sum to less than 1.  Illegal actions' logits are never
+ * read, whatever they hold; a legal -inf gets prior exactly 0; a legal NaN, or every legal logit
+ * -inf, writes the actions, count = m and NaN in every written prior of the row; no legal action:
+ * count 0, all padding.
+ * flags bit 1 (gc_env_sample_policy's bit): the logits are RELATIVE to the side to move -- on a
+ * board whose env state has BLACK to move the logit of legal action a is read at mirror(a) (as
+ * there); the actions written stay absolute.  The side to move comes from the env's current
+ * state, so the mask must describe it.  Bit 0 and every higher bit must be 0.
+ * d_logit_idx (NULL = skip): the element of the logits row each prior was read from -- a, or
+ * mirror(a) on mirrored boards -- so a training step can gather the same logits, or scatter a
+ * visit distribution into the network's view, without knowing the side to move.
+ * Asynchronous on the env's stream; either rule set, either opponent mode.  rows == 0 succeeds
+ * and launches nothing.  Fails (nothing launched) on a NULL env / logits / mask / actions /
+ * priors, an unknown dtype, row_stride < 4100, 0 < mask_stride < n, a temperature that is not
+ * finite or <= 0, an unknown flag bit, cap < 1 or > 4100, rows < 0, rows > n with a NULL index. */
+int gc_env_policy_priors(gc_env* e, const void* d_logits, int dtype, int64_t row_stride,
+                         const uint64_t* d_mask, int64_t mask_stride,
+                         const int32_t* d_board_idx, int rows,
+                         float temperature, int flags, int cap,
+                         uint16_t* d_actions, float* d_priors, int32_t* d_count, uint16_t* d_logit_idx);
 /* The network's input: the env's CURRENT state of every board as GC_PLANES planes of 8x8,
  * written once by one store-bound kernel, asynchronous on the env's stream (after a
  * gc_env_step_device2 with auto-reset it describes what that call's mask / obs / pick describe).
