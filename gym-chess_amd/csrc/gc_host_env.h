@@ -514,6 +514,46 @@ extern "C" int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t*
     return gc_env_step_device2(e, d_actions, d_reward, d_done, d_reason, d_mask, d_obs, d_count, d_pick, flags, 0);
 }
 
+// step() of the listed boards only (gc_step_rows.h): row j steps board d_board_idx[j] under
+// d_actions[j]; row-compact outputs, the mask by board.  One launch, asynchronous on the env's
+// stream; every board not listed, and its mask column, stays as it is.
+extern "C" int gc_env_step_boards(gc_env* e, const int32_t* d_board_idx, const uint16_t* d_actions, int rows,
+                                  int32_t* d_reward, uint8_t* d_done, uint8_t* d_reason, int32_t* d_count,
+                                  uint64_t* d_mask, int64_t mask_stride, int8_t* d_obs, int flags) {
+    if (!e) return fail("null env");
+    if (rows < 0) return fail("negative row count");
+    if (rows > 0 && (!d_board_idx || !d_actions || !d_reward || !d_done || !d_reason)) return fail("null argument");
+    if (flags & ~1) return fail("flags: bit 0 = auto-reset");
+    if (mask_stride != 0 && mask_stride < (int64_t)e->n) return fail("mask stride below the board count");
+    // gc_env_clone_boards' line: a player_color BLACK env's windows can spill into the env's shared
+    // table, whose upkeep (gc_host_spill.h) counts on whole-env stepping calls
+    if (e->d.agent_black || e->d.ic.spill.ent)
+        return fail("step_boards: a player_color BLACK env (spill table) cannot be stepped by board index, as it "
+                    "cannot be cloned; the search envs this serves are opponent \"none\"");
+    if (rows == 0) return 0;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    const int ar = flags & 1;
+    const RowsOut o = {d_reward, d_done, d_reason, d_count, d_mask, d_obs,
+                       mask_stride ? (size_t)mask_stride : (size_t)e->n};
+    const char* bv = getenv("GC_ROWS_BLOCK");  // A/B (read per call): 64-lane or BLOCK-lane workgroups
+    const int block = bv ? (atoi(bv) == BLOCK ? BLOCK : 64) : STEP_ROWS_BLOCK;
+    auto lanes = [&](auto kernel) {  // one lane per row
+        kernel<<<dim3((rows + block - 1) / block), dim3(block), 0, e->stream>>>(e->d, d_board_idx, d_actions, rows, o, ar);
+    };
+    if (e->rules) {  // FIDE
+        if (e->d.opp) lanes(k_fenv_step_rows<true>);
+        else lanes(k_fenv_step_rows<false>);
+    } else if (e->d.opp) {
+        lanes(k_env_step_rows<true>);
+    } else {
+        lanes(k_env_step_rows<false>);
+    }
+    HIPCHK(hipGetLastError());
+    e->policy_ready = false;  // act[] describes the listed boards' earlier positions
+    return 0;
+}
+
 // Policy head on the device (gc_policy.h): per board an action sampled from softmax(logits / T)
 // over the legal mask that gc_env_step_device2 wrote (or the greedy one), its log-prob and the
 // entropy.  Reads only the mask and the logits at legal actions: either rule set, either
@@ -645,6 +685,52 @@ extern "C" int gc_env_encode_planes(gc_env* e, void* d_planes, int dtype, int64_
     if (dtype == 0) { if (nhwc) launch_planes<0, true>(e, a, nt); else launch_planes<0, false>(e, a, nt); }
     else if (dtype == 1) { if (nhwc) launch_planes<1, true>(e, a, nt); else launch_planes<1, false>(e, a, nt); }
     else { if (nhwc) launch_planes<2, true>(e, a, nt); else launch_planes<2, false>(e, a, nt); }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The planes of the listed boards, row-compact (k_encode_planes_rows): row j = board
+// d_board_idx[j].  Read-only like the dense call, so duplicates and any env are fine.
+template <int DT, bool NHWC>
+static void launch_planes_rows(gc_env* e, const PlanesRowsArgs& a, bool nt) {
+    const dim3 grid((a.rows + PLN_WAVES - 1) / PLN_WAVES), block(64 * PLN_WAVES);
+    if (nt) k_encode_planes_rows<DT, NHWC, true><<<grid, block, 0, e->stream>>>(a);
+    else k_encode_planes_rows<DT, NHWC, false><<<grid, block, 0, e->stream>>>(a);
+}
+
+extern "C" int gc_env_encode_planes_rows(gc_env* e, const int32_t* d_board_idx, int rows, void* d_planes,
+                                         int dtype, int64_t row_stride, int flags) {
+    if (!e || !d_planes) return fail("null argument");
+    if (rows < 0) return fail("negative row count");
+    if (rows > 0 && !d_board_idx) return fail("null board index");
+    if (dtype < 0 || dtype > 2) return fail("dtype: 0 float32, 1 float16, 2 bfloat16");
+    if (flags & ~3) return fail("flags: bit 0 = side-to-move view, bit 1 = channels-last");
+    if (row_stride != 0 && row_stride < PLN_ELEMS) return fail("row stride below the 1536 elements of a board");
+    if (row_stride % 8) return fail("row stride must be a multiple of 8 elements");
+    if ((uintptr_t)d_planes % 16) return fail("the planes buffer must be 16-byte aligned");
+    if (rows == 0) return 0;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    PlanesRowsArgs a;
+    a.p.bb = e->d.st.bb;
+    a.p.meta = e->d.st.meta;
+    a.p.hgen = e->d.hgen;
+    a.p.htab = e->d.htab;
+    a.p.sp = e->d.ic.spill;
+    a.p.out = d_planes;
+    a.p.stride = row_stride ? (size_t)row_stride : (size_t)PLN_ELEMS;
+    a.p.n = e->n;
+    a.p.hbits = e->d.hbits;
+    a.p.persp = flags & 1;
+    a.p.fide = e->rules != 0;
+    a.board_idx = d_board_idx;
+    a.rows = rows;
+    const char* ntv = getenv("GC_PLANES_NT");  // A/B (read per call): non-temporal stores
+    const bool nt = ntv ? atoi(ntv) != 0 : PLN_ROWS_NT_DEFAULT;
+    const bool nhwc = (flags & 2) != 0;
+    if (dtype == 0) { if (nhwc) launch_planes_rows<0, true>(e, a, nt); else launch_planes_rows<0, false>(e, a, nt); }
+    else if (dtype == 1) { if (nhwc) launch_planes_rows<1, true>(e, a, nt); else launch_planes_rows<1, false>(e, a, nt); }
+    else { if (nhwc) launch_planes_rows<2, true>(e, a, nt); else launch_planes_rows<2, false>(e, a, nt); }
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -186,3 +186,81 @@ __global__ __launch_bounds__(64 * PLN_WAVES) void k_encode_planes(const PlanesAr
         }
     }
 }
+
+// The indexed form (gc_env_encode_planes_rows): wave = row j of the output, its board read
+// through the index (one scalar load); the network's batch for the nodes a search just expanded.
+// An index outside [0, n) gives an all-zero row: all 1536 elements of every row are written, the
+// stride's padding never.  The body restates k_encode_planes' instead of sharing a function with
+// it: moving that kernel's body into one changed its register allocation, and the dense
+// instantiations are to stay as they are.
+// Stores: a [rows] block is a few MB (3 MiB at 1024 rows of fp16) and is read by the network right
+// away, so plain stores that leave it in the L2 were the candidate.  Measured on an env of 65 536
+// boards, fp16 NCHW side-to-move view (tools/expand_bench.py, GC_PLANES_NT read per call): 3.7-3.9
+// us per launch with either form at 1024 rows, 5.3-5.5 plain against 5.2 non-temporal at 4096 (two
+// runs) -- launch-bound, the forms differ by less than a leg's own spread; the non-temporal one was
+// never the slower, so it is the default here too.  What the network's first read gains from
+// either is not measured.
+#ifndef PLN_ROWS_NT_DEFAULT
+#define PLN_ROWS_NT_DEFAULT true
+#endif
+
+struct PlanesRowsArgs {
+    PlanesArgs p;              // out / stride: the row block's
+    const int32_t* board_idx;  // [rows]
+    int rows;
+};
+
+template <int DT, bool NHWC, bool NT>
+__global__ __launch_bounds__(64 * PLN_WAVES) void k_encode_planes_rows(const PlanesRowsArgs R) {
+    constexpr int EPV = DT == 0 ? 4 : 8;         // elements per 16-byte vector
+    constexpr int STORES = PLN_ELEMS / EPV / 64;  // per lane: 3 (halves) or 6 (floats)
+    const PlanesArgs& A = R.p;
+    const int lane = threadIdx.x & 63;
+    // the row and its board: uniform over the wave, so their loads are scalar
+    const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * PLN_WAVES + (threadIdx.x >> 6));
+    if (j >= R.rows) return;
+    const int i = __builtin_amdgcn_readfirstlane(R.board_idx[j]);
+    pln_vec* out = reinterpret_cast<pln_vec*>(reinterpret_cast<char*>(A.out) + (size_t)j * A.stride * (DT == 0 ? 4 : 2));
+    if ((u32)i >= (u32)A.n) {
+        const pln_vec z = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int st = 0; st < STORES; st++) pln_store<NT>(out + st * 64 + lane, z);
+        return;
+    }
+    const size_t n = (size_t)A.n;
+    Pos s;
+    s.k = A.bb[0 * n + i]; s.q = A.bb[1 * n + i]; s.r = A.bb[2 * n + i]; s.b = A.bb[3 * n + i];
+    s.n = A.bb[4 * n + i]; s.p = A.bb[5 * n + i]; s.w = A.bb[6 * n + i];
+    s.meta = A.meta[i];
+    DevHist h{A.htab, const_cast<u32*>(A.hgen), A.hgen[i], i, A.hbits};
+    h.sp = A.sp;
+    const int rep = rep_peek(h, s);
+    u64 pl[PLN_C];
+    planes_bits(s, rep, A.fide ? gcf::ep_square(s.meta) : -1, A.persp != 0, pl);
+    const u32 vone = pln_raw<DT>(0, true), vmc = pln_raw<DT>(mc_of(s.meta) & 0xFFu, false);
+
+    if (!NHWC) {
+        constexpr int VPP = 64 / EPV, PPS = 64 / VPP;  // vectors per plane, planes per store (k_encode_planes)
+        const int sub = lane / VPP, sq0 = (lane % VPP) * EPV;
+#pragma unroll
+        for (int st = 0; st < STORES; st++) {
+            u64 w = pl[st * PPS];
+#pragma unroll
+            for (int k = 1; k < PPS; k++) w = sub == k ? pl[st * PPS + k] : w;
+            const u32 bits = (u32)(w >> sq0) & ((1u << EPV) - 1u);
+            const bool mc = st * PPS <= PLN_MC && PLN_MC < (st + 1) * PPS && sub == PLN_MC - st * PPS;
+            pln_store<NT>(out + st * 64 + lane, pln_expand<DT>(bits, vone, vmc, -1, mc));
+        }
+    } else {
+        u32 ch = 0;  // the 24 plane bits of square `lane`
+#pragma unroll
+        for (int c = 0; c < PLN_C; c++) ch |= ((u32)(pl[c] >> lane) & 1u) << c;
+#pragma unroll
+        for (int st = 0; st < STORES; st++) {
+            const int v = st * 64 + lane;
+            const int e0 = v * EPV, sq = e0 / PLN_C, c0 = e0 - sq * PLN_C;
+            const u32 bits = ((u32)__shfl((int)ch, sq, 64) >> c0) & ((1u << EPV) - 1u);
+            pln_store<NT>(out + v, pln_expand<DT>(bits, vone, vmc, PLN_MC - c0, false));
+        }
+    }
+}

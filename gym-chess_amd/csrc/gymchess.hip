@@ -4705,6 +4705,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
     e.reason[i] = (uint8_t)o.reason;
 }
 
+#include "gc_step_rows.h"
 #include "gc_planes.h"
 #include "gc_clone.h"
 

@@ -83,7 +83,9 @@ SIGNATURES = {
     "gc_env_rollout_occ_min_plies": (_I, []),
     "gc_env_step_device": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "gc_env_step_device2": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_int64]),
-    "gc_env_sample_policy": (_I, [_P, _P, _I, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, _U64,
+    "gc_env_step_boards": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _I]),
+    "gc_env_encode_planes_rows": (_I, [_P, _P, _I, _P, _I, ctypes.c_int64, _I]),
+    "gc_env_sample_policy": (_I,[_P, _P, _I, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, _U64,
                                   ctypes.c_uint32, _I, _P, _P, _P]),
     "gc_env_policy_priors": (_I, [_P, _P, _I, ctypes.c_int64, _P, ctypes.c_int64, _P, _I, ctypes.c_float, _I, _I,
                                   _P, _P, _P, _P]),

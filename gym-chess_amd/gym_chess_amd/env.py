@@ -59,6 +59,7 @@ class BatchedChessEnv:
         if getattr(self, "_h", None):
             self._clone_free()
             self._priors_free()
+            self._rows_free()
             self._L.gc_env_destroy(self._h)
             self._h = None
 
@@ -403,9 +404,10 @@ class BatchedChessEnv:
     PLANES = 24
     PLANES_LAYOUTS = {"nchw": 0, "nhwc": 2}
 
-    def planes_buffer(self, dtype="float16", layout="nchw", board_stride=None):
-        """device memory for encode_planes: [N][board_stride] elements of `dtype` (None = 24 * 64)"""
-        return PlanesBuffer(self, dtype=dtype, layout=layout, board_stride=board_stride)
+    def planes_buffer(self, dtype="float16", layout="nchw", board_stride=None, rows=None):
+        """device memory for encode_planes: [N][board_stride] elements of `dtype` (None = 24 * 64);
+        rows=m allocates m rows instead of N (encode_planes_rows' output)"""
+        return PlanesBuffer(self, dtype=dtype, layout=layout, board_stride=board_stride, rows=rows)
 
     def encode_planes(self, out, dtype=None, layout=None, perspective=False, board_stride=None):
         """The network's input for the env's current states (gc_env_encode_planes): 24 planes of
@@ -428,6 +430,125 @@ class BatchedChessEnv:
             raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
         _lib.check(self._L.gc_env_encode_planes(self._h, buf.ptr if buf else int(out), self.POLICY_DTYPES[dtype],
                                                 int(board_stride), self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
+
+    def encode_planes_rows(self, out, boards, rows=None, dtype=None, layout=None, perspective=False, row_stride=None):
+        """encode_planes of the listed boards only, row-compact (gc_env_encode_planes_rows): row j
+        of `out` holds the 24 planes of board boards[j] -- the network's batch for the nodes a
+        search just expanded.  out: a planes_buffer(rows=m) (dtype, layout and stride default to
+        the buffer's) or a device pointer (int; defaults float16, "nchw", 24 * 64).  boards: an
+        array-like of board indices (uploaded to this env's staging buffer on its stream, a
+        synchronous copy as clone_boards') or a device pointer (int) to int32[rows], with rows.
+        Duplicates are fine; an index outside [0, N) gives an all-zero row.  Everything else as
+        encode_planes; any env, asynchronous on the env's stream."""
+        buf = out if isinstance(out, PlanesBuffer) else None
+        dtype = dtype if dtype is not None else (buf.dtype if buf else "float16")
+        layout = layout if layout is not None else (buf.layout if buf else "nchw")
+        if row_stride is None:
+            row_stride = buf.board_stride if buf else 0
+        if dtype not in self.POLICY_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
+        if layout not in self.PLANES_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
+        pb, m = self._rows_indices(boards, rows)
+        if buf and m > buf.rows:
+            raise ValueError(f"{m} rows, the planes buffer holds {buf.rows}")
+        _lib.check(self._L.gc_env_encode_planes_rows(self._h, pb, m, buf.ptr if buf else int(out),
+                                                     self.POLICY_DTYPES[dtype], int(row_stride),
+                                                     self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
+
+    # ------------------------------------------------------------------ indexed step (search)
+    BAD_INDEX = 255  # step_boards' reason for a row whose board index is outside [0, N)
+
+    def rows_buffer(self, rows, obs=True, count=True):
+        """device memory for step_boards' row-compact outputs: reward int32[rows], done uint8[rows],
+        reason uint8[rows] and optionally count int32[rows], obs int8[rows][64]"""
+        return RowsBuffer(self, rows, obs=obs, count=count)
+
+    def step_boards(self, io, boards, actions, rows=None, out=None, autoreset=False):
+        """step() of the listed boards only (gc_env_step_boards): board boards[j] takes exactly the
+        step step_device would give it under actions[j]; every other board -- state, 3-fold
+        window, counters, last reward / done / reason -- is untouched.  One launch, asynchronous
+        on the env's stream.
+        boards / actions: array-likes of equal length (int32 / uint16; uploaded to a staging buffer
+        of this env on its stream, a synchronous copy as clone_boards') or device pointers (ints)
+        to int32[rows] / uint16[rows], with rows.  The indices of one call must be distinct; an
+        index outside [0, N) gives reason BAD_INDEX (255), reward 0, done 0, count -1 and a zero
+        obs row, and touches nothing.
+        io: a device_io() whose board-indexed mask takes the 65 words of each listed board (the
+        other boards' words stay, so the buffer accumulates the masks of all tree nodes;
+        policy_priors(io, ..., boards=...) reads it); None = no mask.
+        out: a rows_buffer() for the row-compact reward / done / reason / count / obs; None = a
+        buffer this env keeps and grows.  Returns the buffer used.
+        No pick: the env's policy actions become stale (select_random() before step_random /
+        rollout).  Not for player_color BLACK envs."""
+        pb, m = self._rows_indices(boards, rows)
+        if isinstance(actions, int):
+            pa = actions or None
+        else:
+            a = np.ascontiguousarray(actions, dtype=np.int64).reshape(-1)
+            if a.size != m:
+                raise ValueError(f"{m} boards, {a.size} actions")
+            if (a < 0).any() or (a >= C.N_ACTIONS).any():  # action_space.contains (chess_v2.py:237)
+                raise AssertionError(f"ACTION ERROR {a[(a < 0) | (a >= C.N_ACTIONS)][0]}")
+            a = a.astype(np.uint16)
+            pa = None
+            if m:
+                pa = self._rows_staging(m) + 4 * self._rows_cap
+                _lib.check(self._L.gc_env_copy(self._h, pa, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+        if out is None:
+            if m > getattr(self, "_rows_out_rows", -1):
+                if getattr(self, "_rows_out", None):
+                    self.synchronize()
+                    self._rows_out.close()
+                self._rows_out = RowsBuffer(self, max(256, 1 << max(m - 1, 0).bit_length()))
+                self._rows_out_rows = self._rows_out.rows
+            out = self._rows_out
+        elif not isinstance(out, RowsBuffer):
+            raise TypeError("out must be a rows_buffer()")
+        if m > out.rows:
+            raise ValueError(f"{m} rows, the rows buffer holds {out.rows}")
+        p = out.ptr
+        mask = io.ptr.get("mask") if io is not None else None
+        _lib.check(self._L.gc_env_step_boards(self._h, pb, pa, m, p["reward"], p["done"], p["reason"], p.get("count"),
+                                              mask, io.mask_stride if mask else 0, p.get("obs"),
+                                              int(bool(autoreset))))
+        return out
+
+    def _rows_indices(self, boards, rows):
+        """(device pointer to int32[m], m) of step_boards' / encode_planes_rows' board list"""
+        if isinstance(boards, int):
+            if rows is None:
+                raise ValueError("a device pointer needs rows")
+            return boards or None, int(rows)
+        b = np.ascontiguousarray(boards, dtype=np.int64).reshape(-1)
+        if rows is not None and int(rows) != b.size:
+            raise ValueError(f"rows {rows} != the board array's length {b.size}")
+        b = np.clip(b, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
+        if not b.size:
+            return None, 0
+        pb = self._rows_staging(int(b.size))
+        _lib.check(self._L.gc_env_copy(self._h, pb, _lib.ptr(b), ctypes.c_uint64(b.nbytes), 1))
+        return pb, int(b.size)
+
+    def _rows_staging(self, m):
+        """device int32[cap] boards + uint16[cap] actions for the uploaded lists, grown by doubling"""
+        if m > getattr(self, "_rows_cap", 0):
+            self._rows_free(out=False)  # (gc_device_free waits for the device: no launch still reads it)
+            cap = max(256, 1 << (m - 1).bit_length())
+            v = ctypes.c_void_p()
+            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(6 * cap), ctypes.byref(v)))
+            self._rows_buf, self._rows_cap = v.value, cap
+        return self._rows_buf
+
+    def _rows_free(self, out=True):
+        if getattr(self, "_rows_buf", None):
+            self.synchronize()
+            self._L.gc_device_free(self.device, ctypes.c_void_p(self._rows_buf))
+        self._rows_buf, self._rows_cap = None, 0
+        if out and getattr(self, "_rows_out", None):
+            self.synchronize()
+            self._rows_out.close()
+            self._rows_out, self._rows_out_rows = None, -1
 
     # ------------------------------------------------------------------ board clones (search)
     def clone_boards(self, src, src_idx, dst_idx, count=None):
@@ -560,12 +681,13 @@ class TraceBuffer:
 
 
 class PlanesBuffer:
-    """Device memory of encode_planes' output: [N][board_stride] raw elements of `dtype`
-    (board_stride >= 24 * 64 elements, a multiple of 8)."""
+    """Device memory of encode_planes' output: [rows][board_stride] raw elements of `dtype`
+    (board_stride >= 24 * 64 elements, a multiple of 8; rows = N, or the row count of an
+    encode_planes_rows batch)."""
 
     _RAW = {"float32": np.float32, "float16": np.uint16, "bfloat16": np.uint16}
 
-    def __init__(self, env, dtype="float16", layout="nchw", board_stride=None):
+    def __init__(self, env, dtype="float16", layout="nchw", board_stride=None, rows=None):
         if dtype not in self._RAW:
             raise ValueError(f"dtype must be one of {sorted(self._RAW)}, got {dtype!r}")
         if layout not in env.PLANES_LAYOUTS:
@@ -574,31 +696,81 @@ class PlanesBuffer:
         self.board_stride = int(env.PLANES * 64 if board_stride is None else board_stride)
         if self.board_stride < env.PLANES * 64 or self.board_stride % 8:
             raise ValueError(f"board_stride {self.board_stride}: at least {env.PLANES * 64}, a multiple of 8")
-        self.nbytes = env.num_boards * self.board_stride * np.dtype(self._RAW[dtype]).itemsize
+        self.rows = env.num_boards if rows is None else int(rows)
+        if self.rows < 0:
+            raise ValueError(f"rows {rows} < 0")
+        self.nbytes = self.rows * self.board_stride * np.dtype(self._RAW[dtype]).itemsize
         v = ctypes.c_void_p()
         _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self.nbytes), ctypes.byref(v)))
         self.ptr = v.value
 
     def raw(self):
-        """host copy of the raw elements, [N][board_stride] (float32, or uint16 bit patterns)"""
-        a = np.zeros((self.env.num_boards, self.board_stride), dtype=self._RAW[self.dtype])
-        _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr, ctypes.c_uint64(a.nbytes), 2))
+        """host copy of the raw elements, [rows][board_stride] (float32, or uint16 bit patterns)"""
+        a = np.zeros((self.rows, self.board_stride), dtype=self._RAW[self.dtype])
+        if a.nbytes:
+            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr, ctypes.c_uint64(a.nbytes), 2))
         return a
 
     def fetch(self):
-        """host copy decoded to float32: [N,24,8,8] ("nchw") or [N,8,8,24] ("nhwc")"""
+        """host copy decoded to float32: [rows,24,8,8] ("nchw") or [rows,8,8,24] ("nhwc")"""
         a = self.raw()[:, : self.env.PLANES * 64]
         if self.dtype == "float16":
             a = a.view(np.float16).astype(np.float32)
         elif self.dtype == "bfloat16":
             a = (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
         shape = (24, 8, 8) if self.layout == "nchw" else (8, 8, 24)
-        return np.ascontiguousarray(a).reshape((self.env.num_boards,) + shape)
+        return np.ascontiguousarray(a).reshape((self.rows,) + shape)
 
     def close(self):
         if self.ptr:
             self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(self.ptr))
             self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RowsBuffer:
+    """Device memory of step_boards' row-compact outputs: reward int32[rows], done uint8[rows],
+    reason uint8[rows] and optionally count int32[rows], obs int8[rows][64] (ptr[...] are device
+    pointers; row j belongs to the j-th listed board of the call)."""
+
+    _SPEC = {"reward": (np.int32, ()), "done": (np.uint8, ()), "reason": (np.uint8, ()), "count": (np.int32, ()),
+             "obs": (np.int8, (64,))}
+
+    def __init__(self, env, rows, obs=True, count=True):
+        self.env, self.rows = env, int(rows)
+        if self.rows < 0:
+            raise ValueError(f"rows {rows} < 0")
+        self.ptr = {}
+        for k in ("reward", "done", "reason") + (("count",) if count else ()) + (("obs",) if obs else ()):
+            v = ctypes.c_void_p()
+            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self._shape(k)[1]), ctypes.byref(v)))
+            self.ptr[k] = v.value
+
+    def _shape(self, k):
+        dt, sh = self._SPEC[k]
+        shape = (self.rows,) + sh
+        return shape, int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
+
+    def fetch(self, *keys):
+        """host copies (waits for the env's stream): dict of [rows] / [rows][64] arrays"""
+        out = {}
+        for k in keys or self.ptr:
+            shape, nb = self._shape(k)
+            a = np.zeros(shape, dtype=self._SPEC[k][0])
+            if nb:
+                _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(nb), 2))
+            out[k] = a
+        return out
+
+    def close(self):
+        for v in self.ptr.values():
+            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
+        self.ptr = {}
 
     def __del__(self):
         try:

@@ -173,6 +173,38 @@ int gc_env_step_device(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, 
 int gc_env_step_device2(gc_env* e, const uint16_t* d_actions, int32_t* d_reward, uint8_t* d_done,
                         uint8_t* d_reason, uint64_t* d_mask, int8_t* d_obs, int32_t* d_count,
                         uint16_t* d_pick, int flags, int64_t mask_stride);
+/* One env.step() on the LISTED boards only, for a search that keeps one env state per tree node
+ * and expands a few of them per simulation: for every j < rows, board b = d_board_idx[j] (DEVICE
+ * int32[rows]) takes exactly the step gc_env_step_device2 would give it under action
+ * d_actions[j] (DEVICE uint16[rows], one per ROW) -- the same validation, 3-fold commit, reward /
+ * done / reason, move cap, both-kings-checked handling, opponent reply (opponent "random") and,
+ * with flags bit 0, auto-reset of that board; either rule set.  The board's policy stream is
+ * keyed by b, never by j, so the indexed and the dense step of a board are identical.  The env's
+ * last outputs (gc_env_get_outputs: reward, done, reason, nsteps) of board b are updated as the
+ * dense step updates them.
+ * Outputs, ROW-compact (element j): d_reward, d_done, d_reason, d_count (NULL = skip), d_obs
+ * (NULL = skip; int8[rows][64]).  The mask is BOARD-indexed (NULL = skip): word f of board b at
+ * d_mask[f * mask_stride + b], mask_stride as gc_env_step_device2 (0 = n) -- the env's per-board
+ * mask buffer, the one gc_env_sample_policy and gc_env_policy_priors (d_board_idx) read.  Only the
+ * 65 words of the listed boards are written; every other word keeps its value, so the buffer
+ * accumulates the legal masks of all tree nodes.
+ * Every board that is not listed is untouched, bit for bit: bitboards, meta word, window table
+ * and generation, draw counter, nsteps, reward / done / reason, policy action.  There is no pick
+ * output: the env's policy actions become stale (as after a board clone, below); call
+ * gc_env_select_random before gc_env_step_random / gc_env_rollout.
+ * An index outside [0, n) gives its row reward 0, done 0, reason GC_REASON_BAD_INDEX, count -1
+ * and an all-zero obs row; no board and no mask word is touched, and nothing is accessed out of
+ * bounds whatever the arrays hold.  The caller guarantees that the indices of one call are
+ * distinct; boards named twice end in an unspecified state (every access still in bounds).
+ * One launch, asynchronous on the env's stream, no host synchronisation.  rows == 0 succeeds and
+ * launches nothing.  Fails (nothing launched) on a NULL env, a NULL index / actions / reward /
+ * done / reason with rows > 0, rows < 0, 0 < mask_stride < n, a flag bit above 0, and on a
+ * player_color BLACK env: its 3-fold windows can spill into the env's shared table (the line
+ * the board clone draws, below); the search envs this serves are opponent "none". */
+#define GC_REASON_BAD_INDEX 255
+int gc_env_step_boards(gc_env* e, const int32_t* d_board_idx, const uint16_t* d_actions, int rows,
+                       int32_t* d_reward, uint8_t* d_done, uint8_t* d_reason, int32_t* d_count,
+                       uint64_t* d_mask, int64_t mask_stride, int8_t* d_obs, int flags);
 /* Policy head for a network on the GPU: per board an action drawn from softmax(logits / T) over
  * the legal actions of a mask gc_env_step_device2 wrote, without unpacking the mask or reading
  * the other ~4070 logits of the row.  d_logits: row i at element i * row_stride (>= 4100),
@@ -260,6 +292,17 @@ int gc_env_policy_priors(gc_env* e, const void* d_logits, int dtype, int64_t row
  * bit, 0 < board_stride < 1536, a stride that is no multiple of 8, a misaligned buffer. */
 #define GC_PLANES 24
 int gc_env_encode_planes(gc_env* e, void* d_planes, int dtype, int64_t board_stride, int flags);
+/* gc_env_encode_planes of the listed boards, row-compact: row j of the output (at element j *
+ * row_stride, 0 = 24 * 64) holds the 24 planes of board d_board_idx[j] (DEVICE int32[rows]) --
+ * the network's batch for the nodes a search just expanded, without encoding the whole env.
+ * dtype, flags (side-to-move view, channels-last), plane contents, stride and alignment rules
+ * exactly as gc_env_encode_planes.  Read-only, so duplicates are allowed and any env works
+ * (player_color BLACK included).  An index outside [0, n) gives an all-zero row; all 1536
+ * elements of every row are written (the stride's padding never), so the [rows] block is defined
+ * after the call.  Asynchronous on the env's stream; rows == 0 succeeds and launches nothing.
+ * Fails as gc_env_encode_planes does, and on a NULL index with rows > 0 and rows < 0. */
+int gc_env_encode_planes_rows(gc_env* e, const int32_t* d_board_idx, int rows, void* d_planes,
+                              int dtype, int64_t row_stride, int flags);
 /* Boards copied on the device, for a search that keeps one env state per tree node: for every
  * j < m, board d_dst_idx[j] of `dst` becomes a copy of board d_src_idx[j] of `src` (src == dst
  * is allowed).  Both index arrays are DEVICE memory of m int32.  One launch, asynchronous on
