@@ -1,0 +1,166 @@
+// gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation and
+// the launches of gc_tree.h's kernels, all asynchronous on the tree env's stream.
+#pragma once
+
+struct gc_tree {
+    gc_env* e = nullptr;
+    int device = 0;
+    TreeDev d{};
+    uint8_t* slab = nullptr;  // every array of d, 256-byte aligned, in GC_TREE_ARRAYS order
+    size_t bytes = 0;
+    bool pending = false;  // a selection waits for its backup
+};
+
+// the arrays' sizes in bytes, in the header's order
+static void tree_sizes(size_t G, size_t nodes, size_t cap, size_t out[GC_TREE_ARRAYS]) {
+    const size_t e = G * nodes * cap, n = G * nodes;
+    const size_t s[GC_TREE_ARRAYS] = {2 * e, 4 * e, 4 * e, 4 * e, 4 * e, 4 * n, 4 * n, 4 * n,
+                                      4 * n, n,     4 * G, 4 * G, 4 * G, 4 * G, 4 * G, 8 * n};
+    for (int k = 0; k < GC_TREE_ARRAYS; k++) out[k] = s[k];
+}
+static void tree_addresses(const gc_tree* t, void* out[GC_TREE_ARRAYS]) {
+    const TreeDev& d = t->d;
+    void* p[GC_TREE_ARRAYS] = {d.action,  d.prior,    d.child,       d.edge_visits, d.edge_value, d.n_children,
+                               d.parent,  d.parent_slot, d.leaf_value, d.terminal,    d.n_nodes,    d.overflow,
+                               d.depth,   d.leaf,     d.leaf_new,    d.path};
+    for (int k = 0; k < GC_TREE_ARRAYS; k++) out[k] = p[k];
+}
+static inline dim3 tree_grid(const gc_tree* t) { return dim3((unsigned)((t->d.games + TREE_WAVES - 1) / TREE_WAVES)); }
+
+extern "C" int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out) {
+    if (!e || !out) return fail("null argument");
+    if (games < 1) return fail("games must be >= 1");
+    if (nodes < 1) return fail("nodes must be >= 1");
+    if (cap < 1 || cap > TREE_MAX_CAP) return fail("cap must be in [1, 256]");
+    if ((int64_t)games * nodes > (int64_t)e->n) return fail("games * nodes exceeds the env's boards");
+    HIPCHK(hipSetDevice(e->device));
+    size_t sz[GC_TREE_ARRAYS], off[GC_TREE_ARRAYS], total = 0;
+    tree_sizes((size_t)games, (size_t)nodes, (size_t)cap, sz);
+    for (int k = 0; k < GC_TREE_ARRAYS; k++) {
+        off[k] = total;
+        total += (sz[k] + 255) & ~(size_t)255;
+    }
+    gc_tree* t = new gc_tree();
+    if (dalloc(&t->slab, total)) {
+        delete t;
+        return -1;
+    }
+    hipError_t rc = hipMemsetAsync(t->slab, 0, total, e->stream);
+    if (rc != hipSuccess) {
+        (void)hipFree(t->slab);
+        delete t;
+        return fail(std::string("hipMemsetAsync: ") + hipGetErrorString(rc));
+    }
+    t->e = e;
+    t->device = e->device;
+    t->bytes = total;
+    uint8_t* b = t->slab;
+    TreeDev& d = t->d;
+    d.action = (uint16_t*)(b + off[0]);
+    d.prior = (float*)(b + off[1]);
+    d.child = (int32_t*)(b + off[2]);
+    d.edge_visits = (int32_t*)(b + off[3]);
+    d.edge_value = (float*)(b + off[4]);
+    d.n_children = (int32_t*)(b + off[5]);
+    d.parent = (int32_t*)(b + off[6]);
+    d.parent_slot = (int32_t*)(b + off[7]);
+    d.leaf_value = (float*)(b + off[8]);
+    d.terminal = (uint8_t*)(b + off[9]);
+    d.n_nodes = (int32_t*)(b + off[10]);
+    d.overflow = (int32_t*)(b + off[11]);
+    d.depth = (int32_t*)(b + off[12]);
+    d.leaf = (int32_t*)(b + off[13]);
+    d.leaf_new = (int32_t*)(b + off[14]);
+    d.path = (int32_t*)(b + off[15]);
+    d.games = games;
+    d.nodes = nodes;
+    d.cap = cap;
+    *out = t;
+    return 0;
+}
+
+extern "C" int gc_tree_destroy(gc_tree* t) {
+    if (!t) return fail("null tree");
+    (void)hipSetDevice(t->device);  // (not through e: the env may be gone already)
+    if (t->slab) (void)hipFree(t->slab);  // (waits for the device: no launch still uses the arrays)
+    delete t;
+    return 0;
+}
+
+extern "C" int gc_tree_reset(gc_tree* t, const uint16_t* d_actions, const float* d_priors, const int32_t* d_count,
+                             int pri_cap, const float* d_value) {
+    if (!t) return fail("null tree");
+    if (!d_actions || !d_priors || !d_count) return fail("null priors block");
+    if (pri_cap < 1) return fail("pri_cap must be >= 1");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    const TreePriors p{d_actions, d_priors, d_count, pri_cap};
+    k_tree_reset<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, p, d_value);
+    HIPCHK(hipGetLastError());
+    t->pending = false;
+    return 0;
+}
+
+extern "C" int gc_tree_select(gc_tree* t, float c_puct, float fpu, int32_t* d_parent, int32_t* d_child,
+                              uint16_t* d_action) {
+    if (!t) return fail("null tree");
+    if (!d_parent || !d_child || !d_action) return fail("null output array");
+    if (!std::isfinite(c_puct) || c_puct < 0.f) return fail("c_puct must be finite and >= 0");
+    if (fpu != fpu) return fail("fpu is NaN");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    k_tree_select<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent, d_child,
+                                                                            d_action);
+    HIPCHK(hipGetLastError());
+    t->pending = true;
+    return 0;
+}
+
+extern "C" int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d_done, const uint8_t* d_reason,
+                              const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap) {
+    if (!t) return fail("null tree");
+    if (!d_value || !d_done || !d_reason) return fail("null value / done / reason array");
+    if (!d_actions || !d_priors || !d_count) return fail("null priors block");
+    if (pri_cap < 1) return fail("pri_cap must be >= 1");
+    if (!t->pending) return fail("no selection is pending: gc_tree_select first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    const TreePriors p{d_actions, d_priors, d_count, pri_cap};
+    k_tree_backup<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, d_value, d_done, d_reason, p);
+    HIPCHK(hipGetLastError());
+    t->pending = false;
+    return 0;
+}
+
+extern "C" int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int flags, uint16_t* d_actions,
+                                   int32_t* d_visits, float* d_pi, uint16_t* d_pick, float* d_value) {
+    if (!t) return fail("null tree");
+    if (flags & ~1) return fail("flags: bit 0 = greedy; every other bit 0");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    TreeRootArgs a;
+    a.seed = seed;
+    a.draw = draw;
+    a.greedy = flags & 1;
+    a.actions = d_actions;
+    a.visits = d_visits;
+    a.pi = d_pi;
+    a.pick = d_pick;
+    a.value = d_value;
+    k_tree_root_policy<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gc_tree_pointers(gc_tree* t, void** out, int n) {
+    if (!t || !out) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1");
+    void* p[GC_TREE_ARRAYS];
+    tree_addresses(t, p);
+    for (int k = 0; k < n && k < GC_TREE_ARRAYS; k++) out[k] = p[k];
+    return 0;
+}
+
+extern "C" uint64_t gc_tree_device_bytes(gc_tree* t) { return t ? (uint64_t)t->bytes : 0; }

@@ -1,0 +1,334 @@
+// gc_tree.h -- the batched search tree on the device: per-game node arrays in HBM, a PUCT descent
+// to one leaf per game (k_tree_select), the leaf's expansion and the negamax backup
+// (k_tree_backup), and the root's visit distribution with a move (k_tree_root_policy)
+// (gc_tree_*, include/gymchess.h).
+//
+// Geometry: G games, `nodes` nodes per game, `cap` child slots per node (1..256).  Node k of game
+// g is board g * nodes + k of the tree env; node 0 is the root.  Edge statistics live with the
+// PARENT ([G][nodes][cap]: action, prior, child, edge_visits, edge_value), so one level of the
+// descent is a handful of contiguous loads of one node's row -- no gather through child pointers.
+// edge_value[j] is the sum of the backed-up values seen from the side to move at the parent.
+//
+// Mapping: one wave per game, lanes over the child slots (chunks of 64 when cap > 64), TREE_WAVES
+// games per workgroup; no LDS, no barrier, no atomics (a game is touched by its own wave only, so
+// every result is deterministic).  For cap <= 64 a level of the descent is ONE round trip: the
+// node's n_children and its visits / values / priors / children / actions rows are loaded
+// together (the rows are cap long for every node, so lane < cap is in bounds before n_children is
+// known) and the chosen child comes out of a lane, not out of memory.
+//
+// A node's rows are written when the node is created (k_tree_reset: the root; k_tree_backup: the
+// new leaf), padding included; nodes at or past n_nodes hold whatever an earlier search left.
+#pragma once
+#include "gc_policy.h"
+
+namespace gc {
+
+#define TREE_WAVES 4  // games per workgroup
+#define TREE_MAX_CAP 256
+#define TREE_NO_ACTION 0xFFFFu
+
+struct TreeDev {
+    // [G][nodes][cap]
+    uint16_t* action;
+    float* prior;
+    int32_t* child;
+    int32_t* edge_visits;
+    float* edge_value;
+    // [G][nodes]
+    int32_t* n_children;
+    int32_t* parent;
+    int32_t* parent_slot;
+    float* leaf_value;
+    uint8_t* terminal;
+    // [G]
+    int32_t* n_nodes;
+    int32_t* overflow;
+    int32_t* depth;     // entries of the pending path
+    int32_t* leaf;      // the node the pending path ends at
+    int32_t* leaf_new;  // 1: that node was allotted by the selection and is created by the backup
+    int32_t* path;      // [G][nodes][2]: (node, slot) per level
+    int games, nodes, cap;
+};
+
+// a block of child lists: policy_priors' output, row stride pri_cap
+struct TreePriors {
+    const uint16_t* actions;
+    const float* priors;
+    const int32_t* count;
+    int pri_cap;
+};
+
+using TreeReduceI = hipcub::WarpReduce<int, 64>;
+using TreeReduceD = hipcub::WarpReduce<double, 64>;
+using TreeReduceU64 = hipcub::WarpReduce<unsigned long long, 64>;
+__device__ __forceinline__ int tree_wave_sum(int v) {
+    TreeReduceI::TempStorage ts;
+    return __builtin_amdgcn_readfirstlane(TreeReduceI(ts).Sum(v));
+}
+__device__ __forceinline__ double tree_wave_sum(double v) {
+    TreeReduceD::TempStorage ts;
+    return __shfl(TreeReduceD(ts).Sum(v), 0, 64);
+}
+__device__ __forceinline__ unsigned long long tree_wave_max(unsigned long long v) {
+    TreeReduceU64::TempStorage ts;
+    return __shfl(TreeReduceU64(ts).Reduce(v, hipcub::Max()), 0, 64);
+}
+
+// node `node` of game g (all rows written): its child list = the first min(count, pri_cap, cap)
+// entries of row g of P (none, and the row unread, when !listed: a terminal node), edges zeroed,
+// children -1
+__device__ __forceinline__ void tree_init_node(const TreeDev& T, int g, int node, const TreePriors& P, bool listed,
+                                               int lane) {
+    int m = 0;
+    if (listed) {
+        m = P.count[g];
+        m = m < P.pri_cap ? m : P.pri_cap;
+        m = m < T.cap ? m : T.cap;
+        m = m > 0 ? m : 0;
+    }
+    const size_t nb = (size_t)g * T.nodes + node, o = nb * T.cap, src = (size_t)g * P.pri_cap;
+    for (int s = lane; s < T.cap; s += 64) {
+        const bool on = s < m;
+        T.action[o + s] = on ? P.actions[src + s] : (uint16_t)TREE_NO_ACTION;
+        T.prior[o + s] = on ? P.priors[src + s] : 0.f;
+        T.child[o + s] = -1;
+        T.edge_visits[o + s] = 0;
+        T.edge_value[o + s] = 0.f;
+    }
+    if (lane == 0) T.n_children[nb] = m;
+}
+
+// every game a single root with the child list of row g of P
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_reset(const TreeDev T, const TreePriors P,
+                                                                 const float* __restrict__ value) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    tree_init_node(T, g, 0, P, true, lane);
+    if (lane == 0) {
+        const size_t nb = (size_t)g * T.nodes;
+        T.parent[nb] = -1;
+        T.parent_slot[nb] = -1;
+        T.leaf_value[nb] = value ? value[g] : 0.f;
+        T.terminal[nb] = 0;
+        T.n_nodes[g] = 1;
+        T.overflow[g] = 0;
+        T.depth[g] = 0;
+        T.leaf[g] = 0;
+        T.leaf_new[g] = 0;
+    }
+}
+
+// PUCT descent of every game to one leaf (the header's contract has the rule and the three ways
+// it ends).  score_j = Q_j + c_puct * prior_j * sqrt(n_k) / (1 + visits_j) in fp32, in exactly
+// this order of operations; the largest score wins, ties to the lowest slot.
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T, float c_puct, float fpu,
+                                                                  int32_t* __restrict__ out_parent,
+                                                                  int32_t* __restrict__ out_child,
+                                                                  uint16_t* __restrict__ out_action) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const float ninf = -__builtin_inff();
+    const size_t gb = (size_t)g * T.nodes;
+    const int nn = __builtin_amdgcn_readfirstlane(T.n_nodes[g]);
+    int32_t* path = T.path + gb * 2;
+    int k = 0, D = 0, leaf = 0, is_new = 0;
+    int o_parent = -1, o_child = -1;
+    u32 o_action = TREE_NO_ACTION;
+    // (D < nodes always holds in a tree -- a path visits distinct nodes --; the test bounds the
+    // loop and the path's stores whatever the arrays hold)
+    while (D < T.nodes) {
+        const size_t o = (gb + k) * T.cap;
+        // chunk 0 of the node's rows together with its child count: one round trip
+        const bool in0 = lane < T.cap;
+        int nc = __builtin_amdgcn_readfirstlane(T.n_children[gb + k]);
+        nc = nc < T.cap ? nc : T.cap;
+        int ev0 = in0 ? T.edge_visits[o + lane] : 0;
+        const float val0 = in0 ? T.edge_value[o + lane] : 0.f;
+        const float pr0 = in0 ? T.prior[o + lane] : 0.f;
+        const int ch0 = in0 ? T.child[o + lane] : -1;
+        const u32 ac0 = in0 ? T.action[o + lane] : TREE_NO_ACTION;
+        if (nc <= 0) break;  // (b) a terminal or childless node: the path ends here
+        if (lane >= nc) ev0 = 0;
+        const int chunks = (nc + 63) >> 6;
+        int total = ev0;
+        for (int c = 1; c < chunks; c++) {
+            const int s = c * 64 + lane;
+            total += s < nc ? T.edge_visits[o + s] : 0;
+        }
+        total = tree_wave_sum(total);
+        const float sq = sqrtf((float)(1 + total));
+        auto score = [&](int ev, float val, float pr) {
+            const float q = ev ? val / (float)ev : fpu;
+            return q + c_puct * pr * sq / (float)(1 + ev);
+        };
+        float best = ninf;
+        int j = -1;
+        {
+            const bool on = lane < nc;
+            const float sc = on ? score(ev0, val0, pr0) : ninf;
+            const float mx = pol_wave_max(sc);
+            const unsigned long long hit = __ballot(on && sc == mx);
+            if (hit) {
+                best = mx;
+                j = (int)__builtin_ctzll(hit);
+            }
+        }
+        for (int c = 1; c < chunks; c++) {
+            const int s = c * 64 + lane;
+            const bool on = s < nc;
+            const float sc = on ? score(T.edge_visits[o + s], T.edge_value[o + s], T.prior[o + s]) : ninf;
+            const float mx = pol_wave_max(sc);
+            const unsigned long long hit = __ballot(on && sc == mx);
+            if (hit && (j < 0 || mx > best)) {  // an earlier chunk keeps a tie
+                best = mx;
+                j = c * 64 + (int)__builtin_ctzll(hit);
+            }
+        }
+        if (j < 0) j = 0;  // (only with NaN scores: some slot, in bounds)
+        int ch;
+        u32 ac;
+        if (j < 64) {
+            ch = __builtin_amdgcn_readfirstlane(__shfl(ch0, j, 64));
+            ac = __builtin_amdgcn_readfirstlane(__shfl(ac0, j, 64));
+        } else {
+            ch = __builtin_amdgcn_readfirstlane(T.child[o + j]);
+            ac = __builtin_amdgcn_readfirstlane((u32)T.action[o + j]);
+        }
+        if (lane == 0) {
+            path[2 * D] = k;
+            path[2 * D + 1] = j;
+        }
+        D++;
+        if (ch >= 0 && ch < T.nodes) {  // descend
+            k = ch;
+            continue;
+        }
+        if (nn < T.nodes) {  // (a) a new leaf
+            leaf = nn;
+            is_new = 1;
+            o_parent = (int)(gb + k);
+            o_child = (int)(gb + nn);
+            o_action = ac;
+        } else {  // (c) the game's tree is full: the path ends at k
+            D--;
+            leaf = k;
+            if (lane == 0) T.overflow[g] += 1;
+        }
+        k = -1;
+        break;
+    }
+    if (k >= 0) leaf = k;  // (b)
+    if (lane == 0) {
+        if (is_new) T.n_nodes[g] = nn + 1;
+        T.depth[g] = D;
+        T.leaf[g] = leaf;
+        T.leaf_new[g] = is_new;
+        out_parent[g] = o_parent;
+        out_child[g] = o_child;
+        out_action[g] = (uint16_t)o_action;
+    }
+}
+
+// the pending leaf created (a new one) and its value added along the pending path
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup(const TreeDev T, const float* __restrict__ value,
+                                                                  const uint8_t* __restrict__ done,
+                                                                  const uint8_t* __restrict__ reason,
+                                                                  const TreePriors P) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const size_t gb = (size_t)g * T.nodes;
+    const int D = T.depth[g], L = T.leaf[g];
+    const int32_t* path = T.path + gb * 2;
+    if (D < 0 || D > T.nodes || L < 0 || L >= T.nodes) return;  // (never with a selection pending)
+    float v;
+    if (T.leaf_new[g]) {
+        const bool fin = done[g] != 0;
+        v = fin ? (reason[g] == 1 ? -1.0f : 0.0f) : value[g];  // reason 1: the side to move at L is mated
+        tree_init_node(T, g, L, P, !fin, lane);
+        if (lane == 0 && D > 0) {
+            const int pk = path[2 * (D - 1)], pj = path[2 * (D - 1) + 1];
+            T.parent[gb + L] = pk;
+            T.parent_slot[gb + L] = pj;
+            T.leaf_value[gb + L] = v;
+            T.terminal[gb + L] = fin ? 1 : 0;
+            if ((unsigned)pk < (unsigned)T.nodes && (unsigned)pj < (unsigned)T.cap) T.child[(gb + pk) * T.cap + pj] = L;
+        }
+    } else {
+        v = T.leaf_value[gb + L];
+    }
+    // one lane per path entry: the entries name distinct nodes, so the stores are independent
+    for (int d = lane; d < D; d += 64) {
+        const int k = path[2 * d], j = path[2 * d + 1];
+        if ((unsigned)k >= (unsigned)T.nodes || (unsigned)j >= (unsigned)T.cap) continue;
+        const size_t e = (gb + k) * T.cap + j;
+        T.edge_visits[e] += 1;
+        T.edge_value[e] += ((D - d) & 1) ? -v : v;
+    }
+}
+
+struct TreeRootArgs {
+    uint64_t seed;
+    u32 draw;
+    int greedy;
+    uint16_t* actions;  // [G][cap], may be NULL
+    int32_t* visits;    // [G][cap], may be NULL
+    float* pi;          // [G][cap], may be NULL
+    uint16_t* pick;     // [G], may be NULL
+    float* value;       // [G], may be NULL
+};
+
+// the root's visit counts, their distribution, the root value and a move per game
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const TreeDev T, const TreeRootArgs A) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const size_t o = (size_t)g * T.nodes * T.cap, w = (size_t)g * T.cap;
+    int nc = T.n_children[(size_t)g * T.nodes];
+    nc = nc < T.cap ? nc : T.cap;
+    const int chunks = (T.cap + 63) >> 6;
+    int total = 0;
+    double vsum = 0.0;  // (in fp64 the sum of <= 256 fp32 values is exact but for denormal-sized terms)
+    for (int c = 0; c < chunks; c++) {
+        const int s = c * 64 + lane;
+        if (s < nc) {
+            total += T.edge_visits[o + s];
+            vsum += (double)T.edge_value[o + s];
+        }
+    }
+    total = tree_wave_sum(total);
+    vsum = tree_wave_sum(vsum);
+    if (lane == 0 && A.value) A.value[g] = total > 0 ? (float)(vsum / (double)total) : 0.f;
+    // greedy: the most visited slot, ties to the lowest; sampled: the first slot whose inclusive
+    // visit prefix exceeds r = ((x0 >> 8) * total) >> 24, the sampler's Philox word (gc_policy.h)
+    const u64 r = total > 0 ? (((u64)(philox_x0(A.seed, (u32)g, A.draw) >> 8) * (u64)total) >> 24) : 0;
+    unsigned long long key = 0;  // visits << 32 | ~slot
+    u32 carry = 0;
+    u32 pick = TREE_NO_ACTION;
+    for (int c = 0; c < chunks; c++) {
+        const int s = c * 64 + lane;
+        const bool in = s < T.cap, on = s < nc;
+        const int ev = on ? T.edge_visits[o + s] : 0;
+        const u32 ac = on ? T.action[o + s] : TREE_NO_ACTION;
+        if (in) {
+            if (A.actions) A.actions[w + s] = (uint16_t)ac;
+            if (A.visits) A.visits[w + s] = ev;
+            if (A.pi) A.pi[w + s] = total > 0 ? (float)ev / (float)total : 0.f;
+        }
+        if (A.greedy) {
+            const unsigned long long mine = on ? ((unsigned long long)(u32)ev << 32) | (0xFFFFFFFFu - (u32)s) : 0ull;
+            key = mine > key ? mine : key;
+        } else {
+            const u32 incl = carry + pol_wave_scan((u32)ev);
+            const unsigned long long hit = __ballot(on && (u64)incl > r && (u64)(incl - (u32)ev) <= r);
+            if (hit && pick == TREE_NO_ACTION && total > 0) pick = __shfl(ac, (int)__builtin_ctzll(hit), 64);
+            carry = __shfl(incl, 63, 64);
+        }
+    }
+    if (A.greedy && total > 0) {
+        key = tree_wave_max(key);
+        const int s = (int)(0xFFFFFFFFu - (u32)key);
+        if (s >= 0 && s < nc) pick = T.action[o + s];
+    }
+    if (lane == 0 && A.pick) A.pick[g] = (uint16_t)pick;
+}
+
+}  // namespace gc

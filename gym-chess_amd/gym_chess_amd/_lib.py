@@ -92,6 +92,14 @@ SIGNATURES = {
     "gc_env_encode_planes": (_I, [_P, _P, _I, ctypes.c_int64, _I]),
     "gc_env_clone_boards": (_I, [_P, _P, _P, _P, _I]),
     "gc_env_clone_errors": (_I, [_P, _P]),
+    "gc_tree_create": (_I, [_P, _I, _I, _I, _P]),
+    "gc_tree_destroy": (_I, [_P]),
+    "gc_tree_reset": (_I, [_P, _P, _P, _P, _I, _P]),
+    "gc_tree_select": (_I, [_P, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
+    "gc_tree_backup": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
+    "gc_tree_root_policy": (_I, [_P, _U64, ctypes.c_uint32, _I, _P, _P, _P, _P, _P]),
+    "gc_tree_pointers": (_I, [_P, _P, _I]),
+    "gc_tree_device_bytes": (_U64, [_P]),
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),
     "gc_device_free": (_I, [_I, _P]),

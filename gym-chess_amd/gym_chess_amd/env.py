@@ -19,6 +19,7 @@ reference env's rewards and bookkeeping; an action promotes to a queen.
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
@@ -57,6 +58,11 @@ class BatchedChessEnv:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ref in getattr(self, "_trees", ()):  # search trees launch on this env's stream
+                t = ref()
+                if t is not None:
+                    t.close()
+            self._trees = []
             self._clone_free()
             self._priors_free()
             self._rows_free()
@@ -609,6 +615,17 @@ class BatchedChessEnv:
         _lib.check(self._L.gc_env_clone_errors(self._h, ctypes.byref(v)))
         return int(v.value)
 
+    # ------------------------------------------------------------------ the search tree
+    def search_tree(self, games, nodes, cap=64):
+        """A batched PUCT tree over this (tree) env's boards (gc_tree_*): `games` trees of up to
+        `nodes` nodes with `cap` child slots each; node k of game g is board g * nodes + k.  See
+        SearchTree."""
+        t = SearchTree(self, games, nodes, cap=cap)
+        if not hasattr(self, "_trees"):
+            self._trees = []
+        self._trees.append(weakref.ref(t))
+        return t
+
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""
         v = ctypes.c_void_p()
@@ -816,6 +833,156 @@ class PriorsBuffer:
         for v in self.ptr.values():
             self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
         self.ptr = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DeviceArrays:
+    """device arrays a SearchTree owns: ptr[...] device pointers, fetch() host copies"""
+
+    def __init__(self, env, spec):
+        self.env, self._spec, self.ptr = env, spec, {}
+        for k, (dt, shape) in spec.items():
+            v = ctypes.c_void_p()
+            nb = int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
+            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(nb), ctypes.byref(v)))
+            self.ptr[k] = v.value
+
+    def __getattr__(self, k):
+        ptr = self.__dict__.get("ptr", {})
+        if k in ptr:
+            return ptr[k]
+        raise AttributeError(k)
+
+    def fetch(self, *keys):
+        """host copies (waits for the env's stream)"""
+        out = {}
+        for k in keys or self.ptr:
+            dt, shape = self._spec[k]
+            a = np.zeros(shape, dtype=dt)
+            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
+            out[k] = a
+        return out
+
+    def close(self):
+        for v in self.ptr.values():
+            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
+        self.ptr = {}
+
+
+class SearchTree:
+    """The batched search tree on the device (gc_tree_*, gym-chess_amd/csrc/gc_tree.h): per game a
+    PUCT tree whose child lists are policy_priors' rows.  Every call is one launch, asynchronous on
+    the tree env's stream.  Two-player negamax (an opponent="none" tree env).
+
+        reset(pri, value=None)       every game a single root with the child list of pri's row g
+        sel = select(c_puct, fpu)    one leaf per game: sel.parent / sel.child / sel.action are
+                                     device pointers (int32[G], int32[G], uint16[G]) for
+                                     clone_boards(..., count=G), step_boards(..., rows=G),
+                                     encode_planes_rows and policy_priors(boards=...); rows of
+                                     games without a new leaf hold -1 / -1 / 0xFFFF
+        backup(value, rows, pri)     creates the new leaves (value: device float32[G]; rows: the
+                                     step's rows_buffer, done / reason; pri: their priors) and
+                                     adds each leaf's value along its path, sign alternating
+        root_policy(greedy, seed, draw)   actions / visits / pi / pick / value of every root
+
+    ptr[...] are the device addresses of the tree's arrays (ARRAYS), fetch(*keys) host copies."""
+
+    ARRAYS = ("action", "prior", "child", "edge_visits", "edge_value", "n_children", "parent", "parent_slot",
+              "leaf_value", "terminal", "n_nodes", "overflow", "depth", "leaf", "leaf_new", "path")
+    _DTYPES = {"action": np.uint16, "prior": np.float32, "edge_value": np.float32, "leaf_value": np.float32,
+               "terminal": np.uint8}
+
+    def __init__(self, env, games, nodes, cap=64):
+        self.env, self.games, self.nodes, self.cap = env, int(games), int(nodes), int(cap)
+        self._L = env._L
+        self._h = None
+        h = ctypes.c_void_p()
+        _lib.check(self._L.gc_tree_create(env._h, self.games, self.nodes, self.cap, ctypes.byref(h)))
+        self._h = h
+        addr = (ctypes.c_void_p * len(self.ARRAYS))()
+        _lib.check(self._L.gc_tree_pointers(self._h, addr, len(self.ARRAYS)))
+        self.ptr = {k: addr[i] for i, k in enumerate(self.ARRAYS)}
+        G, C_ = self.games, self.cap
+        self._sel = _DeviceArrays(env, {"parent": (np.int32, (G,)), "child": (np.int32, (G,)),
+                                        "action": (np.uint16, (G,))})
+        self._root = _DeviceArrays(env, {"actions": (np.uint16, (G, C_)), "visits": (np.int32, (G, C_)),
+                                         "pi": (np.float32, (G, C_)), "pick": (np.uint16, (G,)),
+                                         "value": (np.float32, (G,))})
+
+    def _shape(self, k):
+        G, N, C_ = self.games, self.nodes, self.cap
+        if k in ("action", "prior", "child", "edge_visits", "edge_value"):
+            return (G, N, C_)
+        if k in ("n_children", "parent", "parent_slot", "leaf_value", "terminal"):
+            return (G, N)
+        return (G, N, 2) if k == "path" else (G,)
+
+    def _priors(self, pri):
+        if not isinstance(pri, PriorsBuffer):
+            raise TypeError("pri must be a priors_buffer()")
+        if pri.rows < self.games:
+            raise ValueError(f"the priors buffer holds {pri.rows} rows, the tree {self.games} games")
+        return pri.ptr["actions"], pri.ptr["priors"], pri.ptr["count"], pri.cap
+
+    def reset(self, pri, value=None):
+        """every game a single root: children from row g of `pri` (the first min(count, pri.cap,
+        cap)), leaf_value from `value` (a device pointer to float32[G]; None = 0)"""
+        a, p, c, pc = self._priors(pri)
+        _lib.check(self._L.gc_tree_reset(self._h, a, p, c, pc, int(value) if value else None))
+
+    def select(self, c_puct=1.25, fpu=0.0):
+        """the PUCT descent of every game to one leaf; returns the tree's selection buffers
+        (parent / child / action device pointers, .fetch())"""
+        s = self._sel.ptr
+        _lib.check(self._L.gc_tree_select(self._h, float(c_puct), float(fpu), s["parent"], s["child"], s["action"]))
+        return self._sel
+
+    def backup(self, value, rows, pri):
+        """creates the selected leaves and backs their values up (see the class text)"""
+        if not isinstance(rows, RowsBuffer):
+            raise TypeError("rows must be a rows_buffer()")
+        if rows.rows < self.games:
+            raise ValueError(f"the rows buffer holds {rows.rows} rows, the tree {self.games} games")
+        if not value:
+            raise ValueError("value: a device pointer to float32[games]")
+        a, p, c, pc = self._priors(pri)
+        _lib.check(self._L.gc_tree_backup(self._h, int(value), rows.ptr["done"], rows.ptr["reason"], a, p, c, pc))
+
+    def root_policy(self, greedy=False, seed=None, draw=0):
+        """the roots' actions uint16[G][cap], visits int32[G][cap], pi float32[G][cap], value
+        float32[G] and a move pick uint16[G] (greedy: the most visited; else sampled in
+        proportion to the visits from the Philox stream (seed, game, draw); seed None = the
+        env's); returns the tree's buffers (device pointers as attributes, .fetch())"""
+        r = self._root.ptr
+        _lib.check(self._L.gc_tree_root_policy(self._h, ctypes.c_uint64(self.env.seed if seed is None else int(seed)),
+                                               int(draw) & 0xFFFFFFFF, int(bool(greedy)), r["actions"], r["visits"],
+                                               r["pi"], r["pick"], r["value"]))
+        return self._root
+
+    def fetch(self, *keys):
+        """host copies of the tree's arrays (waits for the env's stream)"""
+        out = {}
+        for k in keys or self.ARRAYS:
+            a = np.zeros(self._shape(k), dtype=self._DTYPES.get(k, np.int32))
+            _lib.check(self._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
+            out[k] = a
+        return out
+
+    def device_bytes(self):
+        return int(self._L.gc_tree_device_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gc_tree_destroy(self._h)  # (waits for the device)
+            self._h = None
+            self._sel.close()
+            self._root.close()
+            self.ptr = {}
 
     def __del__(self):
         try:

@@ -335,6 +335,85 @@ int gc_env_clone_boards(gc_env* dst, gc_env* src, const int32_t* d_src_idx, cons
 /* the pairs gc_env_clone_boards skipped into `dst` since its creation (an index out of range);
  * synchronises dst's stream */
 int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
+/* The batched search tree (gc_tree.h): per game a PUCT tree in device memory whose child lists are
+ * gc_env_policy_priors' rows and whose node k of game g is board g * nodes + k of the tree env
+ * `e` -- the arrays gc_tree_select writes feed gc_env_clone_boards / gc_env_step_boards /
+ * gc_env_encode_planes_rows / gc_env_policy_priors(d_board_idx) unchanged.  games >= 1, nodes >= 1
+ * per game, 1 <= cap <= 256 child slots per node, games * nodes <= gc_env_num_boards(e).  Every
+ * call is one launch, asynchronous on e's stream (the stream alone orders it against the env
+ * calls), and none synchronises the host.  `e` must outlive the tree.  Two-player negamax only
+ * (an opponent "none" tree env): no rewards along the path, no discount, no virtual loss, one
+ * leaf per game per call, no subtree reuse across moves.
+ * Arrays (gc_tree_pointers hands out their device addresses in this order; GC_TREE_ARRAYS of them):
+ *    0 action      u16 [games][nodes][cap]   a node's child list, action-id order, padding 0xFFFF
+ *    1 prior       f32 [games][nodes][cap]   padding 0
+ *    2 child       i32 [games][nodes][cap]   node index within the game, -1 = not expanded
+ *    3 edge_visits i32 [games][nodes][cap]
+ *    4 edge_value  f32 [games][nodes][cap]   sum of the backed-up values, from the view of the
+ *                                            side to move AT THIS NODE (the edge's parent)
+ *    5 n_children  i32 [games][nodes]        min(count, pri_cap, cap) of the row it was made from
+ *    6 parent      i32 [games][nodes]        -1 for the root
+ *    7 parent_slot i32 [games][nodes]
+ *    8 leaf_value  f32 [games][nodes]        the value the node was created with, its side's view
+ *    9 terminal    u8  [games][nodes]
+ *   10 n_nodes     i32 [games]
+ *   11 overflow    i32 [games]               selections that wanted a node when the tree was full
+ *   12 depth       i32 [games]               entries of the pending path
+ *   13 leaf        i32 [games]               the node the pending path ends at
+ *   14 leaf_new    i32 [games]               1: gc_tree_backup creates that node
+ *   15 path        i32 [games][nodes][2]     (node, slot) per level of the pending path
+ * The rows of a node are defined from its creation on (padding included); nodes at or past n_nodes
+ * hold whatever an earlier search left (zeros after gc_tree_create).
+ * gc_tree_reset: every game becomes a single root (n_nodes 1, overflow 0) whose child list is the
+ * first min(d_count[g], pri_cap, cap) entries of row g of d_actions / d_priors (row stride
+ * pri_cap: gc_env_policy_priors' output; a count <= 0 gives no children), edges zeroed, children
+ * -1, leaf_value = d_value[g] (NULL: 0).  Clears a pending selection.
+ * gc_tree_select: one wave per game descends from the root.  At node k, in fp32 and in this order
+ * of operations, n = 1 + sum_j edge_visits[j], Q_j = edge_visits[j] ? edge_value[j] /
+ * edge_visits[j] : fpu, score_j = Q_j + c_puct * prior_j * sqrt(n) / (1 + edge_visits[j]) over j <
+ * n_children; the largest score wins, ties go to the lowest slot; (k, j) is appended to the path;
+ * with child[j] >= 0 the descent goes on there.  It ends (a) at child[j] == -1 with n_nodes <
+ * nodes: the new node gets index n_nodes (which is incremented), d_parent[g] = board of k,
+ * d_child[g] = board of the new node, d_action[g] = action[j]; (b) at a terminal or childless
+ * node (a childless root included): d_parent / d_child / d_action = -1 / -1 / 0xFFFF, the path
+ * ends at that node; (c) at child[j] == -1 in a full tree: overflow[g]++, the last path entry is
+ * dropped so that the path ends at k (the pair stays readable at path[depth]), outputs as in
+ * (b).  The downstream env calls skip a -1 row as documented there (clone: skipped and counted;
+ * step_boards: reason 255; planes: a zero row; priors: count -1).  NaN priors give some in-bounds
+ * slot.
+ * gc_tree_backup: per game, for the pending path of D entries ending at leaf L: in case (a) node
+ * L is created -- parent / parent_slot set, the parent's child[slot] = L; with d_done[g] it is
+ * terminal, childless and worth d_reason[g] == 1 (mate: the side to move at L is mated) ? -1 : 0;
+ * otherwise leaf_value = d_value[g] and its child list is row g of the priors block, as in
+ * reset --; in cases (b) and (c) nothing is created and row g of the inputs is not read.  Then
+ * path entry d gets edge_visits += 1 and edge_value += (D - d odd ? -v : v), v = leaf_value[L]:
+ * one fp32 add per edge per simulation, no atomics, so the sums are deterministic.
+ * gc_tree_root_policy: per game the root's actions / visits (padding 0xFFFF / 0 past n_children),
+ * d_pi = visits / sum visits (all 0 without visits), d_value[g] = sum edge_value / sum visits (0
+ * without visits) and a move d_pick[g] (an action id; 0xFFFF without visits or children): flags
+ * bit 0 set = the most visited, ties to the lowest slot; clear = sampled in proportion to the
+ * visits with integers only, r = ((philox_x0(seed, g, draw) >> 8) * total) >> 24 in 64 bits and
+ * the first slot whose inclusive visit prefix exceeds r (gc_env_sample_policy's Philox stream).
+ * Every output may be NULL.  Every other flag bit must be 0.
+ * State: select fails while a selection is pending, backup fails without one, root_policy fails
+ * while one is pending, reset clears it.  Every call fails with nothing launched on a NULL handle
+ * or required pointer (all but reset's d_value and root_policy's outputs), games < 1, nodes < 1,
+ * cap outside 1..256, games * nodes > gc_env_num_boards(e), pri_cap < 1, a c_puct that is not
+ * finite or < 0, a NaN fpu, an unknown flag bit.  gc_tree_pointers writes the first min(n,
+ * GC_TREE_ARRAYS) addresses (n >= 1). */
+#define GC_TREE_ARRAYS 16
+typedef struct gc_tree gc_tree;
+int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out);
+int gc_tree_destroy(gc_tree* t);
+int gc_tree_reset(gc_tree* t, const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap,
+                  const float* d_value);
+int gc_tree_select(gc_tree* t, float c_puct, float fpu, int32_t* d_parent, int32_t* d_child, uint16_t* d_action);
+int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d_done, const uint8_t* d_reason,
+                   const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap);
+int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int flags, uint16_t* d_actions, int32_t* d_visits,
+                        float* d_pi, uint16_t* d_pick, float* d_value);
+int gc_tree_pointers(gc_tree* t, void** out, int n);
+uint64_t gc_tree_device_bytes(gc_tree* t);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */

@@ -1,0 +1,295 @@
+"""Measurement: the device search tree (gc_tree_select + gc_tree_backup) per simulation as the trees
+fill, against a straightforward torch implementation of the same select / backup.
+
+G = 1 024 games, 256 nodes, cap = 64, synthetic child lists (8..40 children, random priors, values
+in [-1, 1], 3 % terminal leaves) -- no chess: the tree kernels see only priors blocks.  Two
+settings of the search: "broad" (c_puct 1.25, fpu 0: shallow trees) and "deep" (c_puct 1.25, fpu
+-1: the descent follows visited children).  Per setting the trees grow over SIMS simulations; the
+us per simulation (select + backup, device events on the env's stream around a window of
+simulations issued without a host synchronisation) is taken in an early window (simulations
+8..40) and a late one (the last 48), with the mean and the largest path length at the end of each
+window; every time is the median of REPS runs after a warm-up run (the per-run values beside it).
+last_select_us / last_backup_us split one simulation on the final trees by events around each
+call (these carry the gaps of the extra event records and are a guide only).
+
+If torch imports and sees the GPU, a child process runs the same simulations on the same inputs
+with the tree as [G][nodes][cap] tensors: per level a gather of the node's rows, the score, an
+argmax and a test whether any game descends further; the backup is a masked scatter along the
+stored paths.  Its windows are timed the same way.  agree = the fraction of games whose root visit
+counts equal the device's at the end.
+
+    python tools/tree_bench.py [--games G] [--nodes N] [--out profiles/tree_search.json]
+"""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gym-chess_amd"))
+
+CAP = 64
+SETTINGS = {"broad": (1.25, 0.0), "deep": (1.25, -1.0)}
+EARLY = (8, 40)
+LATE_LEN = 48
+REPS = 3
+
+
+def median(xs):
+    return float(np.median(np.asarray(xs, dtype=np.float64)))
+
+
+def make_inputs(G, sims, seed=7):
+    """per simulation a priors block [G][CAP] (ascending actions, padded), values, done, reason"""
+    rng = np.random.default_rng(seed)
+    cnt = rng.integers(8, 41, size=(sims + 1, G)).astype(np.int32)
+    w = rng.uniform(0.05, 1.0, size=(sims + 1, G, CAP)).astype(np.float32)
+    on = np.arange(CAP)[None, None, :] < cnt[:, :, None]
+    w = np.where(on, w, 0)
+    pri = (w / w.sum(axis=2, keepdims=True)).astype(np.float32)
+    act = np.where(on, np.arange(CAP, dtype=np.uint16)[None, None, :] * 7, 0xFFFF).astype(np.uint16)
+    val = rng.uniform(-1, 1, size=(sims + 1, G)).astype(np.float32)
+    done = (rng.random((sims + 1, G)) < 0.03).astype(np.uint8)
+    reason = np.where(done != 0, rng.integers(1, 3, size=(sims + 1, G)), 0).astype(np.uint8)
+    return dict(actions=act, priors=pri, count=cnt, value=val, done=done, reason=reason)
+
+
+def windows(sims):
+    return {"early": EARLY, "late": (sims - LATE_LEN, sims)}
+
+
+# ----------------------------------------------------------------------------- the torch leg
+def torch_leg(path, G, nodes, sims):
+    import torch
+
+    if not torch.cuda.is_available():
+        print(json.dumps({"torch": None}))
+        return
+    dev = "cuda"
+    z = np.load(path)
+    inp = {k: torch.from_numpy(z[k].astype(np.int32) if z[k].dtype == np.uint16 else z[k]).to(dev) for k in
+           ("actions", "priors", "count", "value", "done", "reason")}
+    ar = torch.arange(G, device=dev)
+    slots = torch.arange(CAP, device=dev)[None, :]
+    levels = torch.arange(nodes, device=dev)[None, :]
+    out = {"torch": torch.__version__}
+    for name, (c_puct, fpu) in SETTINGS.items():
+        action = torch.full((G, nodes, CAP), 0xFFFF, dtype=torch.int32, device=dev)
+        prior = torch.zeros((G, nodes, CAP), device=dev)
+        child = torch.full((G, nodes, CAP), -1, dtype=torch.int64, device=dev)
+        ev = torch.zeros((G, nodes, CAP), dtype=torch.int32, device=dev)
+        val = torch.zeros((G, nodes, CAP), device=dev)
+        nch = torch.zeros((G, nodes), dtype=torch.int64, device=dev)
+        leaf_value = torch.zeros((G, nodes), device=dev)
+        n_nodes = torch.ones(G, dtype=torch.int64, device=dev)
+        pn = torch.zeros((G, nodes), dtype=torch.int64, device=dev)
+        ps = torch.zeros((G, nodes), dtype=torch.int64, device=dev)
+
+        def make(rows, node, s, listed):
+            """nodes `node` of games `rows` from block s"""
+            m = torch.where(listed, inp["count"][s][rows].clamp(0, CAP).long(), 0)
+            keep = slots < m[:, None]
+            action[rows, node] = torch.where(keep, inp["actions"][s][rows], 0xFFFF)
+            prior[rows, node] = torch.where(keep, inp["priors"][s][rows], 0.0)
+            child[rows, node] = -1
+            ev[rows, node] = 0
+            val[rows, node] = 0.0
+            nch[rows, node] = m
+
+        make(ar, torch.zeros(G, dtype=torch.int64, device=dev), sims, torch.ones(G, dtype=torch.bool, device=dev))
+
+        def select():
+            k = torch.zeros(G, dtype=torch.int64, device=dev)
+            D = torch.zeros(G, dtype=torch.int64, device=dev)
+            live = torch.ones(G, dtype=torch.bool, device=dev)
+            new = torch.zeros(G, dtype=torch.bool, device=dev)
+            while True:
+                e, v, p, nc = ev[ar, k], val[ar, k], prior[ar, k], nch[ar, k]
+                n_k = (1 + e.sum(1)).float()
+                q = torch.where(e > 0, v / e.clamp(min=1), fpu)
+                score = q + c_puct * p * n_k.sqrt()[:, None] / (1 + e)
+                j = score.masked_fill(slots >= nc[:, None], float("-inf")).argmax(1)
+                has = live & (nc > 0)
+                pn[ar, D] = torch.where(has, k, pn[ar, D])
+                ps[ar, D] = torch.where(has, j, ps[ar, D])
+                D = D + has
+                ch = child[ar, k, j]
+                down = has & (ch >= 0)
+                ends = has & ~down
+                room = n_nodes < nodes
+                new = new | (ends & room)
+                D = D - (ends & ~room).long()  # a full tree: the path ends at k
+                k = torch.where(down, ch, k)
+                live = down
+                if not bool(down.any()):
+                    break
+            leaf = torch.where(new, n_nodes, k)
+            n_nodes.add_(new.long())
+            return D, leaf, new
+
+        def backup(D, leaf, new, s):
+            rows = ar[new]
+            L = leaf[new]
+            fin = inp["done"][s][rows] != 0
+            make(rows, L, s, ~fin)
+            last = (D[new] - 1).clamp(min=0)
+            child[rows, pn[rows, last], ps[rows, last]] = L
+            leaf_value[rows, L] = torch.where(fin, torch.where(inp["reason"][s][rows] == 1, -1.0, 0.0),
+                                              inp["value"][s][rows])
+            v = leaf_value[ar, leaf]
+            on = levels < D[:, None]
+            sign = torch.where(((D[:, None] - levels) & 1) == 1, -v[:, None], v[:, None])
+            flat = ((ar[:, None] * nodes + pn) * CAP + ps)[on]
+            ev.view(-1).index_add_(0, flat, torch.ones_like(flat, dtype=torch.int32))
+            val.view(-1).index_add_(0, flat, sign[on])
+
+        res, marks = {}, {a: w for w, (a, b) in windows(sims).items()}
+        ends = {b: w for w, (a, b) in windows(sims).items()}
+        t0 = {}
+        for s in range(sims):
+            if s in marks:
+                torch.cuda.synchronize()
+                t0[marks[s]] = torch.cuda.Event(enable_timing=True)
+                t0[marks[s]].record()
+            D, leaf, new = select()
+            backup(D, leaf, new, s)
+            if s + 1 in ends:
+                w = ends[s + 1]
+                t1 = torch.cuda.Event(enable_timing=True)
+                t1.record()
+                torch.cuda.synchronize()
+                a, b = windows(sims)[w]
+                res[w] = {"torch_us_per_sim": round(t0[w].elapsed_time(t1) * 1e3 / (b - a), 2),
+                          "torch_mean_depth": round(float(D.float().mean()), 2)}
+        agree = (ev[:, 0].cpu().numpy() == z["root_visits_" + name]).all(axis=1).mean()
+        res["agree"] = round(float(agree), 4)
+        out[name] = res
+    print(json.dumps(out))
+
+
+# ----------------------------------------------------------------------------- the device leg
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--games", type=int, default=1024)
+    ap.add_argument("--nodes", type=int, default=256)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--torch-leg", default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    G, nodes = args.games, args.nodes
+    sims = nodes
+    if args.torch_leg:
+        torch_leg(args.torch_leg, G, nodes, sims)
+        return
+
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    env = BatchedChessEnv(G * nodes, device=0, seed=11)
+    L = env._L
+    inp = make_inputs(G, sims)
+
+    def upload(a):
+        v = ctypes.c_void_p()
+        _lib.check(L.gc_device_alloc(env.device, ctypes.c_uint64(a.nbytes), ctypes.byref(v)))
+        _lib.check(L.gc_env_copy(env._h, v.value, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+        return v.value
+
+    d = {k: upload(np.ascontiguousarray(v)) for k, v in inp.items()}
+    tree = env.search_tree(G, nodes, cap=CAP)
+    sel = tree._sel.ptr
+    res = {"games": G, "nodes": nodes, "cap": CAP, "sims": sims, "tree_bytes": tree.device_bytes(),
+           "windows": {w: list(ab) for w, ab in windows(sims).items()}}
+    root_visits = {}
+
+    def block(s):
+        return (d["actions"] + 2 * G * CAP * s, d["priors"] + 4 * G * CAP * s, d["count"] + 4 * G * s, CAP)
+
+    for name, (c_puct, fpu) in SETTINGS.items():
+        def select():
+            _lib.check(L.gc_tree_select(tree._h, c_puct, fpu, sel["parent"], sel["child"], sel["action"]))
+
+        def backup(s):
+            _lib.check(L.gc_tree_backup(tree._h, d["value"] + 4 * G * s, d["done"] + G * s, d["reason"] + G * s,
+                                        *block(s)))
+
+        starts = {a: w for w, (a, b) in windows(sims).items()}
+        ends = {b: w for w, (a, b) in windows(sims).items()}
+        times = {w: [] for w in windows(sims)}
+        out = {}
+        for rep in range(REPS + 1):  # the first run warms up; the trees and so the work are the same every run
+            _lib.check(L.gc_tree_reset(tree._h, *block(sims), None))
+            for s in range(sims):
+                if s in starts:
+                    env.synchronize()
+                    env.record_event(4)
+                select()
+                backup(s)
+                if s + 1 in ends:
+                    w = ends[s + 1]
+                    env.record_event(5)
+                    env.synchronize()
+                    a, b = windows(sims)[w]
+                    if rep:
+                        times[w].append(env.elapsed_ms(4, 5) * 1e3 / (b - a))
+                    dep = tree.fetch("depth", "n_nodes", "overflow")
+                    out[w] = {"mean_depth": round(float(dep["depth"].mean()), 2), "max_depth": int(dep["depth"].max()),
+                              "mean_nodes": round(float(dep["n_nodes"].mean()), 1)}
+        for w, t in times.items():
+            out[w].update({"us_per_sim": round(median(t), 2), "us_per_sim_reps": [round(x, 2) for x in t]})
+        root_visits[name] = tree.fetch("edge_visits")["edge_visits"][:, 0].copy()  # (what the torch leg reaches)
+        # the split of one simulation after the last one (events around each call)
+        ts, tb = [], []
+        for _ in range(20):
+            env.record_event(0)
+            select()
+            env.record_event(1)
+            backup(sims - 1)
+            env.record_event(2)
+            env.synchronize()
+            ts.append(env.elapsed_ms(0, 1) * 1e3)
+            tb.append(env.elapsed_ms(1, 2) * 1e3)
+        out["last_select_us"] = round(median(ts), 2)
+        out["last_backup_us"] = round(median(tb), 2)
+        res[name] = out
+    env.synchronize()
+    tree.close()
+    for p in d.values():
+        L.gc_device_free(env.device, ctypes.c_void_p(p))
+    env.close()
+
+    res["torch"] = None
+    if not args.no_torch:
+        import importlib.util
+
+        if importlib.util.find_spec("torch") is not None:  # a fresh process: torch brings its own HIP runtime
+            with tempfile.TemporaryDirectory() as tmp:
+                path = os.path.join(tmp, "tree.npz")
+                np.savez(path, **inp, **{"root_visits_" + k: v for k, v in root_visits.items()})
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--torch-leg", path, "--games", str(G),
+                                    "--nodes", str(nodes)], capture_output=True, text=True)
+            try:
+                t = json.loads(r.stdout.strip().splitlines()[-1])
+                res["torch"] = t.pop("torch")
+                for name, v in t.items():
+                    for w, x in v.items():
+                        if isinstance(x, dict):
+                            res[name][w].update(x)
+                        else:
+                            res[name]["torch_" + w] = x
+            except Exception:
+                res["torch_error"] = (r.stderr or r.stdout)[-400:]
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
