@@ -15,6 +15,8 @@
 // from a reset, a capture or a pawn move) touches no table at all.  Live entries are written
 // to the same slot positions of the destination's table under its new generation (one bump,
 // which kills whatever the table held).  No LDS, no atomics but the skipped-pair count.
+// The per-pair copy is clone_pair; k_move_boards (at the end) runs it pair after pair inside one
+// wave for the boards gc_tree_advance moves within the tree env.
 // Included by gymchess.hip after DevHist.
 #pragma once
 
@@ -32,16 +34,23 @@ struct CloneArgs {
     int ns, nd, m, hbits;
 };
 
-__global__ __launch_bounds__(64 * CLN_WAVES) void k_clone_boards(const CloneArgs A) {
-    const int lane = threadIdx.x & 63;
-    // the pair: uniform over the wave
-    const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * CLN_WAVES + (threadIdx.x >> 6));
-    if (j >= A.m) return;
-    const int si = __builtin_amdgcn_readfirstlane(A.sidx[j]), di = __builtin_amdgcn_readfirstlane(A.didx[j]);
-    if ((unsigned)si >= (unsigned)A.ns || (unsigned)di >= (unsigned)A.nd) {
-        if (lane == 0) atomicAdd(A.skipped, 1ull);
-        return;
-    }
+// one pair by one wave: board si of the source (in range, uniform over the wave) into board di of
+// the destination (likewise).  Every load of the pair is consumed -- stored, or looked at by the
+// wave's ballot -- before the function returns, so in a wave that copies pair after pair no store
+// of a later pair can overtake a load of an earlier one.  The envs' addresses and sizes come as
+// values, not as a reference to the kernel's CloneArgs: through a reference the compiler no longer
+// proves k_clone_boards' three uniform loads (meta, the two generations) unclobbered and turns
+// them from scalar into vector loads.
+struct ClonePairArgs {
+    const uint8_t* sslab;
+    const u64* stab;
+    uint8_t* dslab;
+    u64* dtab;
+    int ns, nd, hbits;
+};
+__device__ __forceinline__ void clone_pair(const uint8_t* sslab, const u64* stab, uint8_t* dslab, u64* dtab,
+                                           int ns_, int nd_, int hbits, int si, int di, int lane) {
+    const ClonePairArgs A{sslab, stab, dslab, dtab, ns_, nd_, hbits};
     const size_t ns = (size_t)A.ns, nd = (size_t)A.nd;
     const u32* smeta = reinterpret_cast<const u32*>(A.sslab + Slab::meta(ns));
     const u32* shgen = reinterpret_cast<const u32*>(A.sslab + Slab::hgen(ns));
@@ -82,6 +91,50 @@ __global__ __launch_bounds__(64 * CLN_WAVES) void k_clone_boards(const CloneArgs
             if (live) v[u].x = hdr;
             if ((lives >> (lane & ~3)) & 1) dp[hd.entry(base + 16 * u + quad) * 4 + part] = v[u];
             left -= __popcll(lives);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * CLN_WAVES) void k_clone_boards(const CloneArgs A) {
+    const int lane = threadIdx.x & 63;
+    // the pair: uniform over the wave
+    const int j = __builtin_amdgcn_readfirstlane(blockIdx.x * CLN_WAVES + (threadIdx.x >> 6));
+    if (j >= A.m) return;
+    const int si = __builtin_amdgcn_readfirstlane(A.sidx[j]), di = __builtin_amdgcn_readfirstlane(A.didx[j]);
+    if ((unsigned)si >= (unsigned)A.ns || (unsigned)di >= (unsigned)A.nd) {
+        if (lane == 0) atomicAdd(A.skipped, 1ull);
+        return;
+    }
+    clone_pair(A.sslab, A.stab, A.dslab, A.dtab, A.ns, A.nd, A.hbits, si, di, lane);
+}
+
+// Boards moved inside ONE env, game by game (gc_tree_advance): board g * nodes + k of a game with
+// kept[g] > 0 goes to board g * nodes + remap[g][k] for every k with 0 <= remap[g][k] < k (a node
+// that stays where it is needs no copy).  Within a game the pairs overlap: dst_i = base + i is
+// never the source of a LATER pair (sources ascend and lie above their destinations) and no source
+// was an earlier destination, but dst_i can be the source of an EARLIER pair (node 1 becomes the
+// root, its child becomes node 1).  So one wave takes a whole game and copies its pairs one after
+// the other in ascending order; clone_pair consumes every load of a pair before it returns, and
+// the wave's program order puts the next pair's stores after that.  A wave per pair, as
+// k_clone_boards has it, would be wrong here.  Games touch disjoint boards.
+__global__ __launch_bounds__(64 * CLN_WAVES) void k_move_boards(const CloneArgs A, const int32_t* __restrict__ remap,
+                                                                 const int32_t* __restrict__ kept, int games, int nodes) {
+    const int lane = threadIdx.x & 63;
+    const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * CLN_WAVES + (threadIdx.x >> 6));
+    if (g >= games) return;
+    if (__builtin_amdgcn_readfirstlane(kept[g]) <= 0) return;  // a fresh game: no board touched
+    const size_t gb = (size_t)g * nodes;
+    if (gb + nodes > (size_t)A.ns) return;  // (never: games * nodes <= the env's boards)
+    for (int c0 = 0; c0 < nodes; c0 += 64) {
+        const int k = c0 + lane;
+        const int nw = k < nodes ? remap[gb + k] : -1;
+        u64 todo = __ballot(nw >= 0 && nw < k);
+        while (todo) {
+            const int l = (int)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int d = __builtin_amdgcn_readfirstlane(__shfl(nw, l, 64));
+            clone_pair(A.sslab, A.stab, A.dslab, A.dtab, A.ns, A.nd, A.hbits, (int)(gb + c0 + l), (int)(gb + d),
+                       lane);
         }
     }
 }

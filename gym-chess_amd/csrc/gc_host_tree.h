@@ -1,5 +1,6 @@
-// gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation and
-// the launches of gc_tree.h's kernels, all asynchronous on the tree env's stream.
+// gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation (and
+// advance's remap scratch, allocated when first needed) and the launches of gc_tree.h's kernels,
+// all asynchronous on the tree env's stream.
 #pragma once
 
 struct gc_tree {
@@ -7,7 +8,8 @@ struct gc_tree {
     int device = 0;
     TreeDev d{};
     uint8_t* slab = nullptr;  // every array of d, 256-byte aligned, in GC_TREE_ARRAYS order
-    size_t bytes = 0;
+    size_t bytes = 0;         // the slab, plus the remap scratch once it exists
+    int32_t* remap = nullptr;  // [games][nodes]: gc_tree_advance's remap when the caller passes none
     bool pending = false;  // a selection waits for its backup
 };
 
@@ -83,6 +85,7 @@ extern "C" int gc_tree_destroy(gc_tree* t) {
     if (!t) return fail("null tree");
     (void)hipSetDevice(t->device);  // (not through e: the env may be gone already)
     if (t->slab) (void)hipFree(t->slab);  // (waits for the device: no launch still uses the arrays)
+    if (t->remap) (void)hipFree(t->remap);
     delete t;
     return 0;
 }
@@ -130,6 +133,51 @@ extern "C" int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d
     k_tree_backup<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, d_value, d_done, d_reason, p);
     HIPCHK(hipGetLastError());
     t->pending = false;
+    return 0;
+}
+
+extern "C" int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_t* d_actions, const float* d_priors,
+                               const int32_t* d_count, int pri_cap, const float* d_value, int32_t* d_kept,
+                               int32_t* d_remap) {
+    if (!t) return fail("null tree");
+    if (!d_move || !d_kept) return fail("null move / kept array");
+    if (!d_actions || !d_priors || !d_count) return fail("null priors block");
+    if (pri_cap < 1) return fail("pri_cap must be >= 1");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    gc_env* e = t->e;
+    // the board move is a clone within the tree env: refused where gc_env_clone_boards(e, e, ...) is
+    if (e->d.ic.spill.ent)
+        return fail("advance: a player_color BLACK tree env (spill table) cannot move boards; use the checkpoint");
+    if (t->d.nodes > TREE_ADV_MAX_NODES) return fail("advance: nodes exceeds 65536 (the keep bitmap's LDS)");
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    if (!d_remap && !t->remap) {
+        if (dalloc(&t->remap, (size_t)t->d.games * t->d.nodes)) return -1;
+        t->bytes += (size_t)t->d.games * t->d.nodes * sizeof(int32_t);
+    }
+    int32_t* remap = d_remap ? d_remap : t->remap;
+    const TreePriors p{d_actions, d_priors, d_count, pri_cap};
+    const size_t lds = (size_t)TREE_WAVES * ((t->d.nodes + 63) / 64) * sizeof(unsigned long long);
+    k_tree_advance_mark<<<tree_grid(t), dim3(64 * TREE_WAVES), lds, e->stream>>>(t->d, d_move, d_kept, remap);
+    HIPCHK(hipGetLastError());
+    k_tree_advance_compact<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, e->stream>>>(t->d, p, d_value, d_kept, remap);
+    HIPCHK(hipGetLastError());
+    CloneArgs a;
+    a.sslab = e->slab;
+    a.stab = e->d.htab;
+    a.dslab = e->slab;
+    a.dtab = e->d.htab;
+    a.sidx = nullptr;
+    a.didx = nullptr;
+    a.skipped = nullptr;
+    a.ns = e->n;
+    a.nd = e->n;
+    a.m = 0;
+    a.hbits = e->d.hbits;
+    k_move_boards<<<dim3((t->d.games + CLN_WAVES - 1) / CLN_WAVES), dim3(64 * CLN_WAVES), 0, e->stream>>>(
+        a, remap, d_kept, t->d.games, t->d.nodes);
+    HIPCHK(hipGetLastError());
+    e->policy_ready = false;  // act[] describes the moved boards' earlier positions
     return 0;
 }
 

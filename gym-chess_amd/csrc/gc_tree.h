@@ -1,6 +1,7 @@
 // gc_tree.h -- the batched search tree on the device: per-game node arrays in HBM, a PUCT descent
 // to one leaf per game (k_tree_select), the leaf's expansion and the negamax backup
-// (k_tree_backup), and the root's visit distribution with a move (k_tree_root_policy)
+// (k_tree_backup), the root's visit distribution with a move (k_tree_root_policy), and the played
+// move's subtree kept across moves (k_tree_advance_mark / k_tree_advance_compact, at the end)
 // (gc_tree_*, include/gymchess.h).
 //
 // Geometry: G games, `nodes` nodes per game, `cap` child slots per node (1..256).  Node k of game
@@ -10,11 +11,11 @@
 // edge_value[j] is the sum of the backed-up values seen from the side to move at the parent.
 //
 // Mapping: one wave per game, lanes over the child slots (chunks of 64 when cap > 64), TREE_WAVES
-// games per workgroup; no LDS, no barrier, no atomics (a game is touched by its own wave only, so
-// every result is deterministic).  For cap <= 64 a level of the descent is ONE round trip: the
-// node's n_children and its visits / values / priors / children / actions rows are loaded
-// together (the rows are cap long for every node, so lane < cap is in bounds before n_children is
-// known) and the chosen child comes out of a lane, not out of memory.
+// games per workgroup; no LDS (but advance's keep bitmap), no barrier, no atomics (a game is
+// touched by its own wave only, so every result is deterministic).  For cap <= 64 a level of the
+// descent is ONE round trip: the node's n_children and its visits / values / priors / children /
+// actions rows are loaded together (the rows are cap long for every node, so lane < cap is in
+// bounds before n_children is known) and the chosen child comes out of a lane, not out of memory.
 //
 // A node's rows are written when the node is created (k_tree_reset: the root; k_tree_backup: the
 // new leaf), padding included; nodes at or past n_nodes hold whatever an earlier search left.
@@ -98,11 +99,9 @@ __device__ __forceinline__ void tree_init_node(const TreeDev& T, int g, int node
     if (lane == 0) T.n_children[nb] = m;
 }
 
-// every game a single root with the child list of row g of P
-__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_reset(const TreeDev T, const TreePriors P,
-                                                                 const float* __restrict__ value) {
-    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
-    if (g >= T.games) return;
+// game g a single root with the child list of row g of P
+__device__ __forceinline__ void tree_reset_game(const TreeDev& T, int g, const TreePriors& P, const float* value,
+                                                int lane) {
     tree_init_node(T, g, 0, P, true, lane);
     if (lane == 0) {
         const size_t nb = (size_t)g * T.nodes;
@@ -116,6 +115,14 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_reset(const TreeDev T,
         T.leaf[g] = 0;
         T.leaf_new[g] = 0;
     }
+}
+
+// every game a single root with the child list of row g of P
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_reset(const TreeDev T, const TreePriors P,
+                                                                 const float* __restrict__ value) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    tree_reset_game(T, g, P, value, lane);
 }
 
 // PUCT descent of every game to one leaf (the header's contract has the rule and the three ways
@@ -329,6 +336,189 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const Tree
         if (s >= 0 && s < nc) pick = T.action[o + s];
     }
     if (lane == 0 && A.pick) A.pick[g] = (uint16_t)pick;
+}
+
+// ---------------------------------------------------------------------------------------------
+// gc_tree_advance: the played move's subtree kept across moves.  Three launches, each one wave per
+// game: k_tree_advance_mark (which child, the kept set, its ranks -> kept[], remap[][]),
+// k_tree_advance_compact (the tree's rows moved in place, or the game reset) and k_move_boards
+// (gc_clone.h: the boards).  The choices:
+//  * cross-lane traffic: remap[] is written by the lane that owns node k and read by whichever
+//    lane holds a child or parent link to k.  It crosses a KERNEL BOUNDARY: the mark launch only
+//    writes it, the two later launches only read it.  Inside the mark launch the only value one
+//    lane produces and another reads later is the keep bitmap of the earlier chunks; that goes
+//    through LDS (one 64-bit ballot word per chunk, written by lane 0) behind a workgroup-scope
+//    fence, never through global memory.
+//  * LDS bound: TREE_WAVES * ceil(nodes / 64) * 8 bytes of dynamic LDS, so nodes <=
+//    TREE_ADV_MAX_NODES (32 KiB per workgroup); gc_tree_advance refuses a larger tree with a message.
+//  * in-place compaction: ascending old index; row new[k] (new[k] <= k) is written after it was read.
+//    Lane s owns slots s, s + 64, ... of EVERY row in both roles and lane 0 owns the per-node
+//    scalars, so a lane's own program order is the read-before-write ordering.  TREE_ADV_AHEAD
+//    rows are read before the first of them is written (their targets lie at or below the lowest
+//    of them), which shortens the chain of round trips.
+#define TREE_ADV_MAX_NODES 65536
+#define TREE_ADV_AHEAD 4
+
+// which child the move names, the kept set (that child and its descendants) and its stable
+// ranks: kept[g] (0: a fresh game) and remap[g][k] for every k < nodes (-1: not kept)
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_mark(const TreeDev T,
+                                                                        const uint16_t* __restrict__ move,
+                                                                        int32_t* __restrict__ kept,
+                                                                        int32_t* __restrict__ remap) {
+    extern __shared__ unsigned long long tree_adv_bits[];  // [TREE_WAVES][ceil(nodes / 64)]
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const int words = (T.nodes + 63) >> 6;
+    unsigned long long* bits = tree_adv_bits + (size_t)(threadIdx.x >> 6) * words;
+    const size_t gb = (size_t)g * T.nodes;
+    int nn = __builtin_amdgcn_readfirstlane(T.n_nodes[g]);
+    nn = nn < T.nodes ? nn : T.nodes;
+    // the lowest root slot with the move's action and an expanded child
+    const u32 mv = move[g];
+    int nc = __builtin_amdgcn_readfirstlane(T.n_children[gb]);
+    nc = nc < T.cap ? nc : T.cap;
+    int r = -1;
+    if (mv != TREE_NO_ACTION) {
+        for (int c = 0; c * 64 < nc && r < 0; c++) {
+            const int s = c * 64 + lane;
+            const bool on = s < nc;
+            const u32 ac = on ? T.action[gb * T.cap + s] : TREE_NO_ACTION;
+            const int ch = on ? T.child[gb * T.cap + s] : -1;
+            const unsigned long long hit = __ballot(on && ac == mv && ch >= 0 && ch < nn);
+            if (hit) r = __builtin_amdgcn_readfirstlane(__shfl(ch, (int)__builtin_ctzll(hit), 64));
+        }
+    }
+    // keep[k] = k == r || keep[parent[k]], a chain through ascending indices (a parent outside
+    // [0, k) counts as not kept): chunk by chunk, parents of earlier chunks from their ballot
+    // words, parents inside the chunk by iterating the ballot to its fixed point
+    int run = 0;
+    for (int c = 0; c < words; c++) {
+        const int k = c * 64 + lane;
+        const bool live = r >= 0 && k >= r && k < nn;
+        const int p = live ? T.parent[gb + k] : -1;
+        const bool okp = live && p >= r && p < k;
+        const bool inside = okp && (p >> 6) == c;
+        bool kp = live && k == r;
+        if (okp && !inside) kp = (bits[p >> 6] >> (p & 63)) & 1;
+        unsigned long long bal = __ballot(kp);
+        if (__ballot(inside)) {
+            for (;;) {
+                if (inside && ((bal >> (p & 63)) & 1)) kp = true;
+                const unsigned long long nb = __ballot(kp);
+                if (nb == bal) break;
+                bal = nb;
+            }
+        }
+        if (lane == 0) bits[c] = bal;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the word is in LDS before a later chunk reads it
+        if (k < T.nodes) remap[gb + k] = kp ? run + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+        run += __popcll(bal);
+    }
+    if (lane == 0) kept[g] = run;
+}
+
+// a kept game's rows moved to their new indices with the links renumbered; a fresh game reset
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const TreeDev T, const TreePriors P,
+                                                                           const float* __restrict__ value,
+                                                                           const int32_t* __restrict__ kept,
+                                                                           const int32_t* __restrict__ remap) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const int m = __builtin_amdgcn_readfirstlane(kept[g]);
+    if (m <= 0) {
+        tree_reset_game(T, g, P, value, lane);
+        return;
+    }
+    const size_t gb = (size_t)g * T.nodes;
+    const int32_t* rm = remap + gb;
+    int nn = __builtin_amdgcn_readfirstlane(T.n_nodes[g]);
+    nn = nn < T.nodes ? nn : T.nodes;
+    auto renumber = [&](int k) { return (unsigned)k < (unsigned)nn ? rm[k] : -1; };
+    for (int c0 = 0; c0 < nn; c0 += 64) {
+        const int k = c0 + lane;
+        const int nw = k < nn ? rm[k] : -1;
+        unsigned long long todo = __ballot(nw >= 0 && nw <= k);
+        while (todo) {
+            int from[TREE_ADV_AHEAD], to[TREE_ADV_AHEAD];
+#pragma unroll
+            for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                from[u] = to[u] = -1;
+                if (todo) {
+                    const int l = (int)__builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    from[u] = c0 + l;
+                    to[u] = __builtin_amdgcn_readfirstlane(__shfl(nw, l, 64));
+                }
+            }
+            for (int s = lane; s < T.cap; s += 64) {
+                uint16_t ac[TREE_ADV_AHEAD];
+                float pr[TREE_ADV_AHEAD], va[TREE_ADV_AHEAD];
+                int ch[TREE_ADV_AHEAD], ev[TREE_ADV_AHEAD];
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                    if (from[u] < 0) continue;
+                    const size_t o = (gb + from[u]) * T.cap + s;
+                    ac[u] = T.action[o];
+                    pr[u] = T.prior[o];
+                    ch[u] = T.child[o];
+                    ev[u] = T.edge_visits[o];
+                    va[u] = T.edge_value[o];
+                }
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++)
+                    if (from[u] >= 0) ch[u] = renumber(ch[u]);
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                    if (from[u] < 0) continue;
+                    const size_t o = (gb + to[u]) * T.cap + s;
+                    T.action[o] = ac[u];
+                    T.prior[o] = pr[u];
+                    T.child[o] = ch[u];
+                    T.edge_visits[o] = ev[u];
+                    T.edge_value[o] = va[u];
+                }
+            }
+            if (lane == 0) {
+                int nch[TREE_ADV_AHEAD], pa[TREE_ADV_AHEAD], ps[TREE_ADV_AHEAD];
+                float lv[TREE_ADV_AHEAD];
+                uint8_t te[TREE_ADV_AHEAD];
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                    if (from[u] < 0) continue;
+                    const size_t o = gb + from[u];
+                    nch[u] = T.n_children[o];
+                    pa[u] = T.parent[o];
+                    ps[u] = T.parent_slot[o];
+                    lv[u] = T.leaf_value[o];
+                    te[u] = T.terminal[o];
+                }
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                    if (from[u] < 0) continue;
+                    const bool root = to[u] == 0;
+                    pa[u] = root ? -1 : renumber(pa[u]);
+                    ps[u] = root ? -1 : ps[u];
+                }
+#pragma unroll
+                for (int u = 0; u < TREE_ADV_AHEAD; u++) {
+                    if (from[u] < 0) continue;
+                    const size_t o = gb + to[u];
+                    T.n_children[o] = nch[u];
+                    T.parent[o] = pa[u];
+                    T.parent_slot[o] = ps[u];
+                    T.leaf_value[o] = lv[u];
+                    T.terminal[o] = te[u];
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        T.n_nodes[g] = m;
+        T.overflow[g] = 0;
+        T.depth[g] = 0;
+        T.leaf[g] = 0;
+        T.leaf_new[g] = 0;
+    }
 }
 
 }  // namespace gc

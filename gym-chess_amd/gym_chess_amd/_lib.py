@@ -98,6 +98,7 @@ SIGNATURES = {
     "gc_tree_select": (_I, [_P, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
     "gc_tree_backup": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "gc_tree_root_policy": (_I, [_P, _U64, ctypes.c_uint32, _I, _P, _P, _P, _P, _P]),
+    "gc_tree_advance": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "gc_tree_pointers": (_I, [_P, _P, _I]),
     "gc_tree_device_bytes": (_U64, [_P]),
     "gc_env_get_stream": (_I, [_P, _P]),

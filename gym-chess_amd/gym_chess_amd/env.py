@@ -889,6 +889,10 @@ class SearchTree:
                                      step's rows_buffer, done / reason; pri: their priors) and
                                      adds each leaf's value along its path, sign alternating
         root_policy(greedy, seed, draw)   actions / visits / pi / pick / value of every root
+        adv = advance(moves, pri)    between two moves: the played move's subtree becomes the tree
+                                     (nodes renumbered, their boards moved inside the tree env);
+                                     a game without one starts afresh from pri's row g;
+                                     adv.kept / adv.remap are device pointers (int32[G], int32[G][nodes])
 
     ptr[...] are the device addresses of the tree's arrays (ARRAYS), fetch(*keys) host copies."""
 
@@ -913,6 +917,8 @@ class SearchTree:
         self._root = _DeviceArrays(env, {"actions": (np.uint16, (G, C_)), "visits": (np.int32, (G, C_)),
                                          "pi": (np.float32, (G, C_)), "pick": (np.uint16, (G,)),
                                          "value": (np.float32, (G,))})
+        self._adv = _DeviceArrays(env, {"kept": (np.int32, (G,)), "remap": (np.int32, (G, self.nodes))})
+        self._moves = None  # advance()'s staging for uploaded moves, made when first needed
 
     def _shape(self, k):
         G, N, C_ = self.games, self.nodes, self.cap
@@ -964,6 +970,38 @@ class SearchTree:
                                                r["pi"], r["pick"], r["value"]))
         return self._root
 
+    def advance(self, moves, pri, value=None):
+        """Keeps the played move's subtree across moves (gc_tree_advance; three launches on the env's
+        stream).  moves: a device pointer to uint16[G] (root_policy().pick works unchanged) or an
+        array-like of length G, uploaded on the env's stream (a synchronous copy, as step_boards'
+        indices); 0xFFFF marks a game that ended and was reset.  Per game: the root child with that
+        action, if it was expanded, becomes node 0 and its descendants follow in their old order,
+        links renumbered, boards g * nodes + k moved to g * nodes + new[k] (clone semantics, 3-fold
+        windows included); otherwise the game is fresh: a single root from row g of `pri` (a
+        priors_buffer() with at least G rows; rows of kept games are not read) and `value` (a
+        device pointer to float32[G]; None = 0), no board touched -- clone the roots from the game
+        env afterwards (all G of them is always correct).  A device_io()'s board-indexed mask
+        buffer is not moved.  Returns the tree's own buffers: kept int32[G] (the subtree's size, 0
+        = fresh) and remap int32[G][nodes] (new index of every old node, -1 = dropped), device
+        pointers as attributes, .fetch()."""
+        a, p, c, pc = self._priors(pri)
+        if isinstance(moves, int):
+            pm = moves or None
+        else:
+            m = np.ascontiguousarray(moves, dtype=np.int64).reshape(-1)
+            if m.size != self.games:
+                raise ValueError(f"{m.size} moves, the tree holds {self.games} games")
+            if (m < 0).any() or (m > 0xFFFF).any():
+                raise ValueError("moves: action ids, or 0xFFFF for a game that starts afresh")
+            m = m.astype(np.uint16)
+            if self._moves is None:
+                self._moves = _DeviceArrays(self.env, {"moves": (np.uint16, (self.games,))})
+            pm = self._moves.ptr["moves"]
+            _lib.check(self._L.gc_env_copy(self.env._h, pm, _lib.ptr(m), ctypes.c_uint64(m.nbytes), 1))
+        _lib.check(self._L.gc_tree_advance(self._h, pm, a, p, c, pc, int(value) if value else None,
+                                           self._adv.ptr["kept"], self._adv.ptr["remap"]))
+        return self._adv
+
     def fetch(self, *keys):
         """host copies of the tree's arrays (waits for the env's stream)"""
         out = {}
@@ -982,6 +1020,10 @@ class SearchTree:
             self._h = None
             self._sel.close()
             self._root.close()
+            self._adv.close()
+            if self._moves is not None:
+                self._moves.close()
+                self._moves = None
             self.ptr = {}
 
     def __del__(self):

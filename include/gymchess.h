@@ -340,10 +340,10 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * `e` -- the arrays gc_tree_select writes feed gc_env_clone_boards / gc_env_step_boards /
  * gc_env_encode_planes_rows / gc_env_policy_priors(d_board_idx) unchanged.  games >= 1, nodes >= 1
  * per game, 1 <= cap <= 256 child slots per node, games * nodes <= gc_env_num_boards(e).  Every
- * call is one launch, asynchronous on e's stream (the stream alone orders it against the env
- * calls), and none synchronises the host.  `e` must outlive the tree.  Two-player negamax only
- * (an opponent "none" tree env): no rewards along the path, no discount, no virtual loss, one
- * leaf per game per call, no subtree reuse across moves.
+ * call is one launch (gc_tree_advance: three), asynchronous on e's stream (the stream alone orders
+ * it against the env calls), and none synchronises the host.  `e` must outlive the tree.
+ * Two-player negamax only (an opponent "none" tree env): no rewards along the path, no discount,
+ * no virtual loss, one leaf per game per call.
  * Arrays (gc_tree_pointers hands out their device addresses in this order; GC_TREE_ARRAYS of them):
  *    0 action      u16 [games][nodes][cap]   a node's child list, action-id order, padding 0xFFFF
  *    1 prior       f32 [games][nodes][cap]   padding 0
@@ -395,9 +395,42 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * visits with integers only, r = ((philox_x0(seed, g, draw) >> 8) * total) >> 24 in 64 bits and
  * the first slot whose inclusive visit prefix exceeds r (gc_env_sample_policy's Philox stream).
  * Every output may be NULL.  Every other flag bit must be 0.
- * State: select fails while a selection is pending, backup fails without one, root_policy fails
- * while one is pending, reset clears it.  Every call fails with nothing launched on a NULL handle
- * or required pointer (all but reset's d_value and root_policy's outputs), games < 1, nodes < 1,
+ * gc_tree_advance: between two moves of a game, the played move's subtree is kept.  Per game g, j
+ * is the lowest root slot < n_children[root] with action[j] == d_move[g] and 0 <= child[j] <
+ * n_nodes[g].  The game is FRESH when d_move[g] == 0xFFFF (how a caller marks a game that ended
+ * and was reset) or there is no such slot (the move is not in the list, or its child was never
+ * expanded).  KEPT game: with r = child[root][j] the kept set is r and all its descendants,
+ * renumbered by their rank in ascending old index (a stable compaction; a child's index is always
+ * above its parent's, so r becomes node 0 and new[k] < k for every kept k).  Each kept node's
+ * action / prior / edge_visits / edge_value / n_children / leaf_value / terminal / parent_slot
+ * arrive at the new index bit for bit; child[s] becomes new[child[s]] (-1 stays -1), parent becomes
+ * new[parent], the new root gets parent = parent_slot = -1; n_nodes[g] = the size of the kept set,
+ * overflow[g] = 0, depth = leaf = leaf_new = 0; path and the rows at or past the new n_nodes hold
+ * whatever was there.  d_kept[g] = the size of the kept set; d_remap[g][k] (int32 [games][nodes],
+ * may be NULL) = new[k] for a kept node and -1 for every other k < nodes, for callers that keep
+ * per-node data of their own.  Boards: board g * nodes + k of the tree env is moved to board g *
+ * nodes + new[k] for every kept k, with exactly the semantics of gc_env_clone_boards (bitboards,
+ * meta word, last reward / done / reason and the live 3-fold window entries at the same slot
+ * positions copied, the destination's generation bumped, its draw counter, step counter and board
+ * index kept; the env's policy actions become stale); boards at or past d_kept[g] are not
+ * written.  A gc_env_step_boards mask buffer is board-indexed and is NOT moved: it is only ever
+ * read for the child that the same simulation just stepped.  FRESH game: exactly gc_tree_reset for
+ * that one game, from row g of the priors block and d_value[g] (NULL: 0); d_kept[g] = 0, the remap
+ * row all -1, no board touched; rows of kept games in the priors block are not read.  The caller
+ * puts a fresh game's board into the root slot with gc_env_clone_boards(game env -> tree env);
+ * cloning all roots after every advance is always correct (for a kept game the moved board
+ * equals the game env's board whenever the game played that action from that state).
+ * Three launches (mark and rank; the tree's rows; the boards), once per move, asynchronous, no
+ * host synchronisation.  Without d_remap the remap lives in a scratch array of the handle,
+ * allocated by the first such call and counted by gc_tree_device_bytes from then on.  Fails with
+ * nothing launched while a selection is pending (and leaves none pending), on a NULL handle /
+ * d_move / d_kept / priors block, pri_cap < 1, nodes > 65536 (the kernel's keep bitmap lives in
+ * LDS), and where gc_env_clone_boards(e, e, ...) refuses the tree env (player_color BLACK).
+ * Whatever the arrays hold, every access stays in bounds: a parent[k] outside [0, k) counts as
+ * not kept, a child index outside [0, n_nodes) as unexpanded.
+ * State: select fails while a selection is pending, backup fails without one, root_policy and
+ * advance fail while one is pending, reset clears it.  Every call fails with nothing launched on a NULL handle
+ * or required pointer (all but reset's / advance's d_value, advance's d_remap and root_policy's outputs), games < 1, nodes < 1,
  * cap outside 1..256, games * nodes > gc_env_num_boards(e), pri_cap < 1, a c_puct that is not
  * finite or < 0, a NaN fpu, an unknown flag bit.  gc_tree_pointers writes the first min(n,
  * GC_TREE_ARRAYS) addresses (n >= 1). */
@@ -412,6 +445,8 @@ int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d_done, cons
                    const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap);
 int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int flags, uint16_t* d_actions, int32_t* d_visits,
                         float* d_pi, uint16_t* d_pick, float* d_value);
+int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_t* d_actions, const float* d_priors,
+                    const int32_t* d_count, int pri_cap, const float* d_value, int32_t* d_kept, int32_t* d_remap);
 int gc_tree_pointers(gc_tree* t, void** out, int n);
 uint64_t gc_tree_device_bytes(gc_tree* t);
 int gc_env_get_stream(gc_env* e, void** stream);

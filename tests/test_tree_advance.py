@@ -1,0 +1,292 @@
+"""CPU: the reference of gc_tree_advance (the played move's subtree kept across moves,
+gym-chess_amd/csrc/gc_tree.h) on top of test_tree_search's RefTree, checked against a tree built by
+hand and against the tree's own invariants, and the acceptance rule's cap on the runs the GPU tests
+of test_tree_advance_gpu.py make.
+
+AdvTree.advance(moves, actions, priors, count, value) -> (kept [G], remap [G][nodes]): per game the
+lowest root slot whose action is the move and whose child is expanded names the new root r; r and
+its descendants are renumbered by rank in ascending old index, their rows move to the new indices
+bit for bit with child / parent links renumbered, the new root's parent / parent_slot become -1;
+without such a slot (or with the move 0xFFFF) the game is reset from row g of the block.  Rows at
+or past the new n_nodes keep whatever they held.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import test_tree_search as R
+
+NONE = R.NONE
+ROOT = R.ROOT
+ABSENT = 5000  # no synthetic child list holds it (their actions are below 4100)
+EDGE_KEYS = ("action", "prior", "child", "edge_visits", "edge_value")
+SCALAR_KEYS = ("n_children", "parent", "parent_slot", "leaf_value", "terminal")
+
+
+class AdvTree(R.RefTree):
+    def new_root(self, g, move):
+        """the node the move leads to, -1 for a fresh game"""
+        if int(move) == NONE:
+            return -1
+        for j in range(int(self.n_children[g, 0])):
+            if self.action[g, 0, j] == move and 0 <= self.child[g, 0, j] < self.n_nodes[g]:
+                return int(self.child[g, 0, j])
+        return -1
+
+    def advance(self, moves, actions, priors, count, value=None):
+        G, N = self.games, self.nodes
+        kept = np.zeros(G, dtype=np.int32)
+        remap = np.full((G, N), -1, dtype=np.int32)
+        pri_cap = actions.shape[1]
+        for g in range(G):
+            r, nn = self.new_root(g, moves[g]), int(self.n_nodes[g])
+            if r < 0:  # exactly reset(), for this game
+                self._init_node(g, 0, actions, priors, count, pri_cap)
+                self.parent[g, 0] = self.parent_slot[g, 0] = -1
+                self.leaf_value[g, 0] = np.float32(0 if value is None else value[g])
+                self.terminal[g, 0] = 0
+                self.n_nodes[g] = 1
+            else:
+                keep = np.zeros(nn, dtype=bool)
+                keep[r] = True
+                for k in range(r + 1, nn):
+                    p = int(self.parent[g, k])
+                    keep[k] = 0 <= p < k and keep[p]
+                old = np.flatnonzero(keep)
+                new = remap[g]
+                new[old] = np.arange(old.size)
+                for key in EDGE_KEYS + SCALAR_KEYS:  # (fancy indexing copies the right side first)
+                    a = getattr(self, key)
+                    a[g, : old.size] = a[g, old]
+                ch = self.child[g, : old.size]
+                ch[ch >= 0] = new[ch[ch >= 0]]
+                self.parent[g, 1: old.size] = new[self.parent[g, 1: old.size]]
+                self.parent[g, 0] = self.parent_slot[g, 0] = -1
+                self.n_nodes[g] = kept[g] = old.size
+            self.overflow[g] = self.depth[g] = self.leaf[g] = self.leaf_new[g] = 0
+        return kept, remap
+
+
+def check_links(t):
+    """parent / child / parent_slot agree with each other, and a child's index is above its parent's"""
+    for g in range(t.games):
+        n = int(t.n_nodes[g])
+        assert n >= 1 and t.parent[g, 0] == -1 and t.parent_slot[g, 0] == -1, g
+        for k in range(n):
+            nc = int(t.n_children[g, k])
+            assert (t.child[g, k, nc:] == -1).all() and (t.action[g, k, nc:] == NONE).all(), (g, k)
+            for s in range(nc):
+                c = int(t.child[g, k, s])
+                if c >= 0:
+                    assert k < c < n and t.parent[g, c] == k and t.parent_slot[g, c] == s, (g, k, s, c)
+            if k:
+                p, s = int(t.parent[g, k]), int(t.parent_slot[g, k])
+                assert 0 <= p < k and 0 <= s < t.n_children[g, p] and t.child[g, p, s] == k, (g, k, p, s)
+            if t.terminal[g, k]:
+                assert nc == 0, (g, k)
+
+
+# --------------------------------------------------------------------------- a tree built by hand
+def test_advance_by_hand():
+    """Four games with the tree of test_three_simulations_by_hand (root 100 / 200 and a third
+    child 250 with prior 0, which is never visited): node 1 under slot 0 (value +0.5), node 2 under
+    slot 1 (value -0.25), node 3 under node 2 (mate).  Game 0 plays 200: nodes 2, 3 become 0, 1.
+    Game 1 is marked 0xFFFF, game 2 plays 250 (never expanded), game 3 plays an action that is not
+    in the list: all three start afresh from their row of the block."""
+    G = 4
+    t = AdvTree(G, 4, 3)
+    t.reset(*R._block([[(100, 0.6), (200, 0.4), (250, 0.0)]] * G, 3))
+    leaf = R._block([[(300, 1.0)]] * G, 3)
+    full = lambda x, dt: np.full(G, x, dtype=dt)
+    for v, dn, why in ((0.5, 0, 0), (-0.25, 0, 0), (0.9, 1, 1)):
+        t.select(1.0, 0.0)
+        t.backup(full(v, np.float32), full(dn, np.uint8), full(why, np.uint8), *leaf)
+    assert (t.n_nodes == 4).all() and t.child[0, 0].tolist() == [1, 2, -1] and t.child[0, 2].tolist() == [3, -1, -1]
+    assert t.edge_visits[0, 0].tolist() == [1, 2, 0]
+    stale = {k: getattr(t, k).copy() for k in EDGE_KEYS + SCALAR_KEYS}
+
+    block = R._block([[(10 + g, 0.75), (20 + g, 0.25)] for g in range(G)], 3)
+    value = np.array([0.125, 0.25, 0.375, 0.5], dtype=np.float32)
+    kept, remap = t.advance(np.array([200, NONE, 250, 999], dtype=np.uint16), *block, value=value)
+    assert kept.tolist() == [2, 0, 0, 0]
+    assert remap.tolist() == [[-1, -1, 0, 1]] + [[-1] * 4] * 3
+    assert t.n_nodes.tolist() == [2, 1, 1, 1]
+    for key in R.GAME_KEYS[1:]:
+        assert not getattr(t, key).any(), key
+    # game 0: the old node 2 is the root, the mated node 3 its only child
+    assert t.action[0, 0].tolist() == [300, NONE, NONE] and t.prior[0, 0].tolist() == [1.0, 0.0, 0.0]
+    assert t.child[0, 0].tolist() == [1, -1, -1] and t.edge_visits[0, 0].tolist() == [1, 0, 0]
+    assert t.edge_value[0, 0].tolist() == [1.0, 0.0, 0.0]
+    assert (t.n_children[0, 0], t.parent[0, 0], t.parent_slot[0, 0], t.terminal[0, 0]) == (1, -1, -1, 0)
+    assert t.leaf_value[0, 0] == np.float32(-0.25)
+    assert t.action[0, 1].tolist() == [NONE] * 3 and t.child[0, 1].tolist() == [-1] * 3
+    assert (t.n_children[0, 1], t.parent[0, 1], t.parent_slot[0, 1], t.terminal[0, 1]) == (0, 0, 0, 1)
+    assert t.leaf_value[0, 1] == -1.0 and not t.edge_visits[0, 1].any()
+    for key in stale:  # the rows at or past n_nodes are left alone
+        assert getattr(t, key)[0, 2:].tobytes() == stale[key][0, 2:].tobytes(), key
+    # games 1..3: a single root from their row of the block
+    for g in (1, 2, 3):
+        assert t.action[g, 0].tolist() == [10 + g, 20 + g, NONE] and t.prior[g, 0].tolist() == [0.75, 0.25, 0.0]
+        assert t.child[g, 0].tolist() == [-1] * 3 and not t.edge_visits[g, 0].any() and not t.edge_value[g, 0].any()
+        assert (t.n_children[g, 0], t.parent[g, 0], t.parent_slot[g, 0], t.terminal[g, 0]) == (2, -1, -1, 0)
+        assert t.leaf_value[g, 0] == value[g]
+        for key in stale:
+            assert getattr(t, key)[g, 1:].tobytes() == stale[key][g, 1:].tobytes(), key
+    check_links(t)
+    r = t.root_policy(0, 0, True)
+    assert r["pick"].tolist() == [300, NONE, NONE, NONE]
+    # the search goes on from the kept tree: the root's only child is the mated node
+    p, c, a = t.select(1.0, 0.0)
+    assert t.depth.tolist() == [1, 1, 1, 1] and t.leaf[0] == 1 and not t.leaf_new[0] and c[0] == -1
+    assert c[1:].tolist() == [5, 9, 13] and a[1:].tolist() == [11, 12, 13]
+
+
+# --------------------------------------------------------------------------- synthetic runs
+# the GPU tests' runs (test_tree_advance_gpu.py): shapes (G, nodes, cap) as the issue lists them --
+# ragged against 4 games per workgroup, a chain, and more than one 64-slot chunk -- with the rule,
+# seed, c_puct and fpu of the SYNTH_CASES entry of that shape (a low fpu: deep trees, so the kept
+# subtrees are large)
+ADV_CASES = [R.SYNTH_CASES[i] for i in (0, 2, 3, 5, 7)]
+MOVE_RULES = ("greedy", "unexpanded", "fresh", "absent")
+
+
+def advance_blocks(case, n=2):
+    """the priors blocks and values of a run's advances"""
+    G, nodes, cap, rule, seed = case[:5]
+    rng = np.random.RandomState(seed + 1000)
+    pc = R.pri_cap_of(cap, rule)
+    return [R.synth_rows(rng, G, cap, pc) + (rng.uniform(-1, 1, size=G).astype(np.float32),) for _ in range(n)]
+
+
+def moves_for(t, greedy, turn):
+    """the moves of one advance: game g follows MOVE_RULES[(g - turn) % 4] -- the greedy pick, the
+    action of the root's first unexpanded child (0xFFFF without one), 0xFFFF, an action no list holds"""
+    mv = np.full(t.games, NONE, dtype=np.uint16)
+    for g in range(t.games):
+        rule = MOVE_RULES[(g - turn) % 4]
+        if rule == "greedy":
+            mv[g] = greedy[g]
+        elif rule == "unexpanded":
+            free = np.flatnonzero(t.child[g, 0, : t.n_children[g, 0]] < 0)
+            mv[g] = t.action[g, 0, free[0]] if free.size else NONE
+        elif rule == "absent":
+            mv[g] = ABSENT
+    return mv
+
+
+def stages(nodes):
+    """simulations before the first advance, between the two, and after"""
+    return (0, nodes), (nodes, nodes + nodes // 2), (nodes + nodes // 2, 2 * nodes)
+
+
+def run_alone(case, nodes=None, all_greedy=False, hook=None):
+    """the reference driven alone through the GPU tests' sequence: `nodes` simulations, advance,
+    nodes / 2 more, advance, the rest; hook(t, turn, old, moves, kept, remap) after each advance"""
+    G, n0, cap, rule, seed, c_puct, fpu = case
+    inp = R.synth_run(G, n0, cap, rule, seed)
+    t = AdvTree(G, nodes or n0, cap)
+    t.reset(*inp["root"], value=inp["root_value"])
+    blocks = advance_blocks(case)
+    for turn, (a, b) in enumerate(stages(n0)):
+        for s in range(a, b):
+            t.select(c_puct, fpu)
+            t.backup(inp["value"][s], inp["done"][s], inp["reason"][s], inp["actions"][s], inp["priors"][s],
+                     inp["count"][s])
+        if turn == 2:
+            break
+        greedy = t.root_policy(0, 0, True)["pick"]
+        mv = greedy.copy() if all_greedy else moves_for(t, greedy, turn)
+        old = {k: getattr(t, k).copy() for k in EDGE_KEYS + SCALAR_KEYS + ("n_nodes", "overflow")}
+        act, pri, cnt, val = blocks[turn]
+        kept, remap = t.advance(mv, act, pri, cnt, value=val)
+        if hook:
+            hook(t, turn, old, mv, kept, remap)
+    return t
+
+
+@pytest.mark.parametrize("case", R.SYNTH_CASES)
+def test_invariants_on_synthetic_runs(case):
+    """SYNTH_CASES' shapes in trees of 2 * nodes + 1 nodes, which 2 * nodes simulations cannot fill;
+    every game plays its greedy pick.  After each advance: the links are consistent and ascending;
+    the kept set is the new root's old subtree, in its old order; a kept root that has children
+    holds the visits of the edge that led to it but the one that created it (a childless or
+    terminal root holds none: every visit ended at it).  The second advance works on trees whose
+    rows past n_nodes hold the first one's leftovers."""
+    G, n0, cap = case[:3]
+    seen = dict(kept=0, moved=0, stale=0)
+
+    def hook(t, turn, old, mv, kept, remap):
+        check_links(t)
+        assert (t.overflow == 0).all()
+        for g in range(G):
+            seen["stale"] += int(turn == 0 and t.n_nodes[g] < old["n_nodes"][g])  # (leftovers past n_nodes)
+            r = -1
+            for j in range(int(old["n_children"][g, 0])):
+                if old["action"][g, 0, j] == mv[g] and old["child"][g, 0, j] >= 0:
+                    r = int(old["child"][g, 0, j])
+                    break
+            if r < 0:
+                assert kept[g] == 0 and (remap[g] == -1).all() and t.n_nodes[g] == 1
+                continue
+            ks = np.flatnonzero(remap[g] >= 0)
+            assert ks[0] == r and (remap[g, ks] == np.arange(ks.size)).all() and kept[g] == ks.size == t.n_nodes[g]
+            assert (remap[g, ks] < ks).all()
+            anc = {r}  # the subtree, by walking the old parents
+            for k in range(r + 1, int(old["n_nodes"][g])):
+                if int(old["parent"][g, k]) in anc:
+                    anc.add(k)
+            assert sorted(anc) == ks.tolist(), g
+            for key in ("action", "prior", "edge_visits", "edge_value", "n_children", "leaf_value", "terminal"):
+                assert getattr(t, key)[g, : ks.size].tobytes() == old[key][g, ks].tobytes(), (key, g)
+            assert (t.parent_slot[g, 1: ks.size] == old["parent_slot"][g, ks[1:]]).all()
+            led = int(old["edge_visits"][g, 0, j])
+            if t.n_children[g, 0] > 0:
+                assert t.edge_visits[g, 0].sum() == led - 1, (g, led)
+            else:
+                assert t.edge_visits[g, 0].sum() == 0
+            seen["kept"] += 1
+            seen["moved"] += int(ks.size > 1)
+
+    t = run_alone(case, nodes=2 * n0 + 1, all_greedy=True, hook=hook)
+    check_links(t)
+    assert (t.overflow == 0).all()
+    assert seen["kept"] >= G and seen["moved"] >= 1 and seen["stale"] >= 1, seen
+
+
+@pytest.mark.parametrize("case", ADV_CASES)
+def test_near_ties_are_rare_across_advances(case):
+    """the acceptance rule's cap for the reference alone on every run the GPU tests make, and every
+    move rule occurs in them with its effect"""
+    G = case[0]
+    seen = set()
+
+    def hook(t, turn, old, mv, kept, remap):
+        check_links(t)
+        for g in range(G):
+            rule = MOVE_RULES[(g - turn) % 4]
+            if rule != "greedy":
+                assert kept[g] == 0, (g, rule)
+            seen.add((rule, bool(kept[g])))
+
+    t = run_alone(case, hook=hook)
+    assert t.decisions > 100
+    assert t.near_ties < 0.01 * t.decisions, (t.near_ties, t.decisions)
+    assert ("greedy", True) in seen and {("unexpanded", False), ("fresh", False), ("absent", False)} <= seen
+
+
+# --------------------------------------------------------------------------- the binding
+def test_advance_is_declared_and_bound():
+    import re
+
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import SearchTree
+
+    src = open(os.path.join(ROOT, "include", "gymchess.h")).read()
+    assert "no subtree reuse" not in src
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    assert "gc_tree_advance" in set(re.findall(r"\b(gc_[a-z0-9_]+)\s*\(", src))
+    assert re.search(r"#define\s+GC_TREE_ARRAYS\s+16\b", src)
+    assert len(_lib.SIGNATURES["gc_tree_advance"][1]) == 9
+    assert getattr(_lib.load(), "gc_tree_advance") is not None
+    assert callable(getattr(SearchTree, "advance", None))

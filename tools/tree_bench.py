@@ -18,7 +18,19 @@ argmax and a test whether any game descends further; the backup is a masked scat
 stored paths.  Its windows are timed the same way.  agree = the fraction of games whose root visit
 counts equal the device's at the end.
 
+--advance measures gc_tree_advance instead (the played move's subtree kept across moves): per
+setting the trees grow over nodes - 1 simulations, root_policy picks greedily and the trees advance
+on that pick.  advance_us and reset_us (a gc_tree_reset of the same trees) are medians of REPS runs
+after a warm-up, by events on the env's stream around the call; kept_mean / kept_max are the kept
+subtrees' sizes, retained_visits_mean the mean of the new roots' visit sums (what the next search
+starts with), tree_us_per_sim the mean select + backup time over the same run's simulations, and
+saved_us_lower_bound = retained_visits_mean * tree_us_per_sim (the tree's share alone of
+re-searching the retained visits; the network's time comes on top).  The tree env's boards all
+stand at the start position, whose 3-fold window is empty: the board move copies the per-board
+fields only, a window costs what tools/clone_bench.py measures per pair.
+
     python tools/tree_bench.py [--games G] [--nodes N] [--out profiles/tree_search.json]
+    python tools/tree_bench.py --advance [--out profiles/tree_advance.json]
 """
 import argparse
 import ctypes
@@ -172,6 +184,81 @@ def torch_leg(path, G, nodes, sims):
     print(json.dumps(out))
 
 
+# ----------------------------------------------------------------------------- advance
+def advance_leg(G, nodes, out_path):
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    sims = nodes - 1
+    env = BatchedChessEnv(G * nodes, device=0, seed=11)
+    L = env._L
+    inp = make_inputs(G, sims + 1)
+
+    def upload(a):
+        v = ctypes.c_void_p()
+        _lib.check(L.gc_device_alloc(env.device, ctypes.c_uint64(a.nbytes), ctypes.byref(v)))
+        _lib.check(L.gc_env_copy(env._h, v.value, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+        return v.value
+
+    d = {k: upload(np.ascontiguousarray(v)) for k, v in inp.items()}
+    tree = env.search_tree(G, nodes, cap=CAP)
+    sel, adv = tree._sel.ptr, tree._adv.ptr
+    res = {"games": G, "nodes": nodes, "cap": CAP, "sims": sims, "reps": REPS}
+
+    def block(s):
+        return (d["actions"] + 2 * G * CAP * s, d["priors"] + 4 * G * CAP * s, d["count"] + 4 * G * s, CAP)
+
+    for name, (c_puct, fpu) in SETTINGS.items():
+        t_adv, t_reset, t_sim = [], [], []
+        out = {}
+        for rep in range(REPS + 1):  # the first run warms up; the trees are the same every run
+            _lib.check(L.gc_tree_reset(tree._h, *block(sims), None))
+            env.synchronize()
+            env.record_event(0)
+            for s in range(sims):
+                _lib.check(L.gc_tree_select(tree._h, c_puct, fpu, sel["parent"], sel["child"], sel["action"]))
+                _lib.check(L.gc_tree_backup(tree._h, d["value"] + 4 * G * s, d["done"] + G * s, d["reason"] + G * s,
+                                            *block(s)))
+            env.record_event(1)
+            pick = tree.root_policy(greedy=True).pick
+            env.synchronize()
+            nodes_before = tree.fetch("n_nodes")["n_nodes"]
+            env.record_event(2)
+            _lib.check(L.gc_tree_advance(tree._h, pick, *block(sims + 1), None, adv["kept"], adv["remap"]))
+            env.record_event(3)
+            env.synchronize()
+            kept = tree._adv.fetch("kept")["kept"]
+            retained = tree.fetch("edge_visits")["edge_visits"][:, 0].sum(axis=1)
+            env.record_event(4)
+            _lib.check(L.gc_tree_reset(tree._h, *block(sims), None))
+            env.record_event(5)
+            env.synchronize()
+            if rep:
+                t_sim.append(env.elapsed_ms(0, 1) * 1e3 / sims)
+                t_adv.append(env.elapsed_ms(2, 3) * 1e3)
+                t_reset.append(env.elapsed_ms(4, 5) * 1e3)
+            out = {"nodes_before_mean": round(float(nodes_before.mean()), 1),
+                   "kept_mean": round(float(kept.mean()), 2), "kept_max": int(kept.max()),
+                   "fresh_games": int((kept == 0).sum()),
+                   "retained_visits_mean": round(float(retained.mean()), 2)}
+        out.update({"advance_us": round(median(t_adv), 2), "advance_us_reps": [round(x, 2) for x in t_adv],
+                    "reset_us": round(median(t_reset), 2), "reset_us_reps": [round(x, 2) for x in t_reset],
+                    "tree_us_per_sim": round(median(t_sim), 2)})
+        out["advance_minus_reset_us"] = round(out["advance_us"] - out["reset_us"], 2)
+        out["saved_us_lower_bound"] = round(out["retained_visits_mean"] * out["tree_us_per_sim"], 1)
+        res[name] = out
+    env.synchronize()
+    tree.close()
+    for p in d.values():
+        L.gc_device_free(env.device, ctypes.c_void_p(p))
+    env.close()
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+
+
 # ----------------------------------------------------------------------------- the device leg
 def main():
     ap = argparse.ArgumentParser()
@@ -179,12 +266,16 @@ def main():
     ap.add_argument("--nodes", type=int, default=256)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--advance", action="store_true", help="measure gc_tree_advance (see the module text)")
     ap.add_argument("--torch-leg", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     G, nodes = args.games, args.nodes
     sims = nodes
     if args.torch_leg:
         torch_leg(args.torch_leg, G, nodes, sims)
+        return
+    if args.advance:
+        advance_leg(G, nodes, args.out)
         return
 
     from gym_chess_amd import _lib
