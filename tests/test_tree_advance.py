@@ -1,7 +1,8 @@
 """CPU: the reference of gc_tree_advance (the played move's subtree kept across moves,
 gym-chess_amd/csrc/gc_tree.h) on top of test_tree_search's RefTree, checked against a tree built by
-hand and against the tree's own invariants, and the acceptance rule's cap on the runs the GPU tests
-of test_tree_advance_gpu.py make.
+hand and against the tree's own invariants, the acceptance rule's cap on the runs the GPU tests
+of test_tree_advance_gpu.py make, and what their large runs reach (kept subtrees across several
+64-node chunks).
 
 AdvTree.advance(moves, actions, priors, count, value) -> (kept [G], remap [G][nodes]): per game the
 lowest root slot whose action is the move and whose child is expanded names the new root r; r and
@@ -159,12 +160,17 @@ def advance_blocks(case, n=2):
     return [R.synth_rows(rng, G, cap, pc) + (rng.uniform(-1, 1, size=G).astype(np.float32),) for _ in range(n)]
 
 
-def moves_for(t, greedy, turn):
+def moves_for(t, greedy, turn, first_greedy=False, g0=0):
     """the moves of one advance: game g follows MOVE_RULES[(g - turn) % 4] -- the greedy pick, the
-    action of the root's first unexpanded child (0xFFFF without one), 0xFFFF, an action no list holds"""
+    action of the root's first unexpanded child (0xFFFF without one), 0xFFFF, an action no list holds.
+    first_greedy (the large runs' rule): at the first advance every game plays its greedy pick, so
+    the games of one workgroup keep subtrees side by side; the second advance rotates as above.
+    g0: the place in the rotation of t's first game (a game taken out of a larger run)"""
+    if first_greedy and turn == 0:
+        return np.asarray(greedy, dtype=np.uint16).copy()
     mv = np.full(t.games, NONE, dtype=np.uint16)
     for g in range(t.games):
-        rule = MOVE_RULES[(g - turn) % 4]
+        rule = MOVE_RULES[(g0 + g - turn) % 4]
         if rule == "greedy":
             mv[g] = greedy[g]
         elif rule == "unexpanded":
@@ -180,11 +186,12 @@ def stages(nodes):
     return (0, nodes), (nodes, nodes + nodes // 2), (nodes + nodes // 2, 2 * nodes)
 
 
-def run_alone(case, nodes=None, all_greedy=False, hook=None):
+def run_alone(case, nodes=None, all_greedy=False, hook=None, make=None, first_greedy=False):
     """the reference driven alone through the GPU tests' sequence: `nodes` simulations, advance,
-    nodes / 2 more, advance, the rest; hook(t, turn, old, moves, kept, remap) after each advance"""
+    nodes / 2 more, advance, the rest; hook(t, turn, old, moves, kept, remap) after each advance.
+    make: the inputs (R.synth_run, or R.open_run); first_greedy: moves_for's"""
     G, n0, cap, rule, seed, c_puct, fpu = case
-    inp = R.synth_run(G, n0, cap, rule, seed)
+    inp = (make or R.synth_run)(G, n0, cap, rule, seed)
     t = AdvTree(G, nodes or n0, cap)
     t.reset(*inp["root"], value=inp["root_value"])
     blocks = advance_blocks(case)
@@ -196,7 +203,7 @@ def run_alone(case, nodes=None, all_greedy=False, hook=None):
         if turn == 2:
             break
         greedy = t.root_policy(0, 0, True)["pick"]
-        mv = greedy.copy() if all_greedy else moves_for(t, greedy, turn)
+        mv = greedy.copy() if all_greedy else moves_for(t, greedy, turn, first_greedy)
         old = {k: getattr(t, k).copy() for k in EDGE_KEYS + SCALAR_KEYS + ("n_nodes", "overflow")}
         act, pri, cnt, val = blocks[turn]
         kept, remap = t.advance(mv, act, pri, cnt, value=val)
@@ -273,6 +280,54 @@ def test_near_ties_are_rare_across_advances(case):
     assert t.decisions > 100
     assert t.near_ties < 0.01 * t.decisions, (t.near_ties, t.decisions)
     assert ("greedy", True) in seen and {("unexpanded", False), ("fresh", False), ("absent", False)} <= seen
+
+
+@pytest.mark.parametrize("idx", range(len(R.LARGE_CASES)), ids=lambda i: "{}x{}x{}".format(*R.LARGE_CASES[i][:3]))
+def test_large_runs_cross_the_chunks(idx):
+    """what makes the GPU tests over LARGE_CASES meaningful, on the reference alone (a chunk is
+    k >> 6, the 64 nodes one pass of the advance kernels takes): at the first advance, where every
+    game plays its greedy pick, at least two games of the first workgroup keep subtrees that lie
+    in two chunks or more (three in cases 0 and 1); kept nodes have their parent in an earlier
+    chunk (the keep bitmap read back) and, past node 64, in their own (the fixed point of a
+    chunk entered from outside); in case 0 a parent lies two chunks back; in cases 0 and 2 a node
+    past 64 is dropped with kept ones after it (ranks carried across a gap); the chain moves down
+    by one as a whole.  Another seed has to meet the same conditions."""
+    case = R.LARGE_CASES[idx]
+    G, nodes, cap = case[:3]
+    seen = dict(cross=0, inside=0, far=0, gap=0)
+    spans = []  # turn 0: chunks of the kept set, per game of the first workgroup
+
+    def hook(t, turn, old, mv, kept, remap):
+        check_links(t)
+        for g in range(G):
+            ks = np.flatnonzero(remap[g] >= 0)
+            assert ks.size == kept[g]
+            if turn == 0 and g < 4:
+                spans.append(np.unique(ks >> 6).size)
+            if turn == 0 and cap == 1:
+                n = int(old["n_nodes"][g])
+                assert kept[g] == n - 1 and (remap[g, 1:n] == np.arange(n - 1)).all() and remap[g, 0] == -1, g
+            if ks.size < 2:
+                continue
+            rest = ks[1:]  # (ks[0] is the new root)
+            back = (rest >> 6) - (old["parent"][g, rest] >> 6)
+            seen["cross"] += int((back >= 1).sum())
+            seen["far"] += int((back >= 2).sum())
+            seen["inside"] += int(((back == 0) & (rest >= 64)).sum())
+            dropped = np.flatnonzero(remap[g, : ks[-1]] < 0)
+            seen["gap"] += int((dropped >= 64).sum())
+
+    t = run_alone(case, hook=hook, make=R.open_run, first_greedy=True)
+    print(f"chunks per game at the first advance {spans}, {seen}, near ties {t.near_ties} of {t.decisions}")
+    need = 3 if idx in (0, 1) else 2
+    assert sum(s >= need for s in spans) >= 2, spans
+    assert seen["cross"] >= 1 and seen["inside"] >= 1, seen
+    if idx == 0:
+        assert seen["far"] >= 1, seen
+    if idx in (0, 2):
+        assert seen["gap"] >= 1, seen
+    assert t.decisions > 100
+    assert t.near_ties < 0.01 * t.decisions, (t.near_ties, t.decisions)
 
 
 # --------------------------------------------------------------------------- the binding

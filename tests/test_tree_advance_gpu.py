@@ -1,6 +1,7 @@
 """GPU: gc_tree_advance / SearchTree.advance (the played move's subtree kept across moves) against
-AdvTree of test_tree_advance.py: synthetic trees at every cap that takes another path, placement
-and repeatability, the boards of the kept nodes in the documented chess loop under both rule sets
+AdvTree of test_tree_advance.py: synthetic trees at every cap that takes another path, trees of
+several 64-node chunks (alone and side by side in one workgroup), the node bound, placement and
+repeatability, the boards of the kept nodes in the documented chess loop under both rule sets
 (the in-place board move's ordering), and the state and argument errors.  Buffers come from
 gc_device_alloc / gc_env_copy; no torch."""
 import ctypes
@@ -43,12 +44,13 @@ def put_block(env, pri, block):
 
 
 # --------------------------------------------------------------------------- 1. synthetic trees
-def run_sequence(env, case, G, inp, blocks, check=True, shots=None):
+def run_sequence(env, case, G, inp, blocks, check=True, shots=None, first_greedy=False, g0=0):
     """junk-filled arrays -> `nodes` simulations -> advance -> nodes / 2 more -> advance -> the
     rest, the reference following every selection under the acceptance rule.  The moves reach the
     device as root_policy's pick buffer (the greedy picks stay as the kernel wrote them; the other
     rules' moves are written over theirs).  shots: a list that takes the device's arrays after
-    each advance and at the end."""
+    each advance and at the end.  first_greedy, g0: A.moves_for's (the large runs' move rule; a
+    game taken out of a larger run)."""
     _, nodes, cap, rule, seed, c_puct, fpu = case
     r = T.Run(env, G, nodes, cap, inp, c_puct, fpu)
     r.ref = A.AdvTree(G, nodes, cap)
@@ -63,14 +65,14 @@ def run_sequence(env, case, G, inp, blocks, check=True, shots=None):
         T.fill_arrays(env, tree._root)
         rp = tree.root_policy(greedy=True)
         picks = rp.fetch("pick")["pick"]
-        mv = A.moves_for(r.ref, picks, turn) if check else None
+        mv = A.moves_for(r.ref, picks, turn, first_greedy, g0) if check else None
         if check:
             assert (picks == r.ref.root_policy(0, 0, True)["pick"]).all()
         else:  # (placement runs: the reference is not driven, the rules come from the device's tree)
             d = tree.fetch("child", "action", "n_children")
             shadow = A.AdvTree(G, nodes, cap)
             shadow.child, shadow.action, shadow.n_children = d["child"], d["action"], d["n_children"]
-            mv = A.moves_for(shadow, picks, turn)
+            mv = A.moves_for(shadow, picks, turn, first_greedy, g0)
         for g in np.flatnonzero(mv != picks):
             upload(env, rp.pick + 2 * int(g), mv[g: g + 1])
         act, prs, cnt, val = blocks[turn]
@@ -107,7 +109,54 @@ def test_synthetic_trees(env, case):
     assert ref.near_ties < 0.01 * ref.decisions, (ref.near_ties, ref.decisions)
 
 
+@pytest.fixture(scope="module")
+def large_env():
+    """boards for the trees of R.LARGE_CASES (5 x 200 nodes)"""
+    from gym_chess_amd.env import BatchedChessEnv
+
+    e = BatchedChessEnv(1000, device=0, seed=3)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("case", R.LARGE_CASES, ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}")
+def test_large_synthetic_trees(large_env, case):
+    """test_synthetic_trees on trees of 130 and 200 nodes (R.open_run's inputs; every game plays its
+    greedy pick at the first advance, so games 0 to 2 keep subtrees of several 64-node chunks inside
+    one workgroup -- A.test_large_runs_cross_the_chunks has what the runs reach): the keep bitmap
+    read back across chunks, the ranks carried on, the rows and boards moved from later chunks into
+    earlier ones"""
+    G = case[0]
+    ref = run_sequence(large_env, case, G, R.open_run(*case[:5]), A.advance_blocks(case), first_greedy=True)
+    assert ref.near_ties < 0.01 * ref.decisions, (ref.near_ties, ref.decisions)
+
+
 # --------------------------------------------------------------------------- 2. placement
+def test_large_placement(large_env):
+    """game 1 of R.LARGE_CASES[0] through the whole sequence: the same bits alone (G = 1: the
+    workgroup's first wave, its keep bitmap at the start of the LDS block) and as one of five (the
+    second wave, its bitmap one tree's words further on, between those of games 0 and 2, which
+    keep subtrees too)"""
+    case = R.LARGE_CASES[0]
+    inp, blocks = R.open_run(*case[:5]), A.advance_blocks(case)
+    one_blocks = [tuple(np.ascontiguousarray(x[1:2]) for x in b) for b in blocks]
+    same = lambda x, y: np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes()
+    five, one = [], []
+    run_sequence(large_env, case, 5, inp, blocks, check=False, shots=five, first_greedy=True)
+    run_sequence(large_env, case, 1, T._game0(inp, 1), one_blocks, check=False, shots=one, first_greedy=True, g0=1)
+    assert (five[0]["kept"][:3] > 64).all(), five[0]["kept"]  # games 0 to 2 keep more than a chunk
+    for turn, (a, c) in enumerate(zip(five[:2], one[:2])):
+        n = int(a["n_nodes"][1])
+        assert n == c["n_nodes"][0] and a["kept"][1] == c["kept"][0] and a["kept"][1] > 1, (turn, a["kept"], c["kept"])
+        assert same(a["remap"][1], c["remap"][0]), turn
+        for key in R.NODE_KEYS:
+            assert same(a[key][1][:n], c[key][0][:n]), (turn, key)
+    n = int(five[2]["n_nodes"][1])  # the end of the run
+    assert n == one[2]["n_nodes"][0]
+    for key in R.NODE_KEYS:
+        assert same(five[2][key][1][:n], one[2][key][0][:n]), key
+
+
 def test_placement_and_repeatability(env):
     """game 0 through the whole sequence: the same bits alone (G = 1) and as one of five, and in a
     second run (all five games, junk included)"""
@@ -175,20 +224,31 @@ def continue_pairs(a, aio, ia, b, bio, ib, steps):
     return verdicts
 
 
+# (G, NODES, SIMS, MORE): the second one's trees span two 64-node chunks of k_move_boards and
+# k_tree_advance_compact.  The shuffling games 0..3 do not get there at any size: their most
+# visited move leads to the draw by repetition, which takes the visits without growing (they keep 3
+# to 7 nodes of 72 or 128); the games on random moves keep up to 90 of 96
+BOARD_GEOMETRIES = [(8, 17, 16, 8), (8, 96, 95, 8)]
+
+
+@pytest.mark.parametrize("geo", BOARD_GEOMETRIES, ids=lambda g: f"{g[0]}x{g[1]}")
 @pytest.mark.parametrize("rules", ["reference", "fide"])
-def test_boards_follow_their_nodes(rules):
-    """The documented loop with chess: 8 games 6 plies in (games 0..3 on test_clone_gpu's knight
-    shuffle, the others on seeded random moves), trees of 17 nodes, 16 simulations with fpu -1
+def test_boards_follow_their_nodes(rules, geo):
+    """The documented loop with chess: G games 6 plies in (games 0..3 on test_clone_gpu's knight
+    shuffle, the others on seeded random moves), trees of NODES nodes, SIMS simulations with fpu -1
     (deep trees) on seeded pseudo-logits that favour the shuffle's four moves -- so the shuffling
     games tend to play Ng1 and keep a subtree whose boards carry the shuffle's live window and, two
     plies down, the draw by repetition --, then root_policy -> the game env's step -> policy_priors
-    on the game env -> advance -> the roots cloned, and 8 more simulations.
+    on the game env -> advance -> the roots cloned, and MORE more simulations.
     Before the advance the whole tree env is cloned into a shadow env at the same indices; after it
-    board g * 17 + new[k] must be the shadow's board g * 17 + k in every way a clone is compared,
-    and every board at or past kept[g] must be as it was."""
+    board g * NODES + new[k] must be the shadow's board g * NODES + k in every way a clone is
+    compared, and every board at or past kept[g] must be as it was.  With more than 64 nodes a
+    board also moves from node 64 or later to an earlier index, and a game's kept set lies in both
+    chunks."""
     from gym_chess_amd.env import BatchedChessEnv
 
-    G, NODES, CAP, SIMS, MORE = 8, 17, 64, 16, 8
+    G, NODES, SIMS, MORE = geo
+    CAP = 64
     C_PUCT, FPU = 1.25, -1.0
     rng = np.random.RandomState(41)
     game = BatchedChessEnv(G, device=0, seed=5, rules=rules)
@@ -269,6 +329,13 @@ def test_boards_follow_their_nodes(rules):
     hazards = sum(int(remap[g, k] >= 0 and remap[g, remap[g, k]] >= 0) for g in range(G) for k in range(NODES))
     print(f"{rules}: kept {kept.tolist()}, {src.size} boards moved, {hazards} onto the source of an earlier pair")
     assert src.size >= G and hazards >= 1, (kept, hazards)
+    if NODES > 64:
+        moved = [np.flatnonzero((remap[g] >= 0) & (remap[g] < np.arange(NODES))) for g in range(G)]
+        spans = [np.unique(np.flatnonzero(remap[g] >= 0) >> 6).size for g in range(G)]
+        print(f"{rules}: moved from node 64 or later {[int((m >= 64).sum()) for m in moved]}, chunks kept {spans}")
+        assert any((m >= 64).any() for m in moved), kept  # a source in the second chunk
+        assert any(((m >= 64) & (remap[g, m] < 64)).any() for g, m in enumerate(moved)), kept  # ... into the first
+        assert max(spans) >= 2, spans  # a kept set in both chunks
     rest = np.setdiff1d(everything, dst)
     assert (rest % NODES >= kept[rest // NODES]).all()
     lens = [len(CG.window(shadow, int(i))) for i in src]
@@ -399,3 +466,74 @@ def test_state_and_argument_errors(env):
     black.close()
     for b in (a, p, c, v, done, mv, small, full):
         b.close()
+
+
+# --------------------------------------------------------------------------- 5. the node bound
+def test_the_node_bound():
+    """TREE_ADV_MAX_NODES = 65 536 (the keep bitmap's 32 KiB of LDS per workgroup), on one env of
+    65 537 boards.  A tree of 65 537 nodes: advance is refused with a message that names the bound,
+    and neither the tree nor kept / remap change.  A tree of 65 536 nodes over junk-filled arrays:
+    a one-move root, three simulations with one-move lists (a chain of four nodes), advance on the
+    greedy pick -> kept = 3, remap = the reference's over all 65 536 entries (1 024 ballot words,
+    the largest launch the bound allows), the tree = the reference's below n_nodes."""
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    BOUND = 65536
+    e = BatchedChessEnv(BOUND + 1, device=0, seed=3)
+    L = e._L
+    blocks = [R._block([[(100 + s, 1.0)]], 1) for s in range(5)]  # the root, three leaves, the advance's
+    dev = [[Dev(e, x) for x in b] for b in blocks]
+    zero, val = Dev(e, np.zeros(1, dtype=np.uint8)), Dev(e, np.array([0.375], dtype=np.float32))
+    mv = Dev(e, np.array([100], dtype=np.uint16))
+
+    # above the bound
+    tree = e.search_tree(1, BOUND + 1, cap=1)
+    T.fill_tree(e, tree)
+    _lib.check(L.gc_tree_reset(tree._h, *(b.ptr for b in dev[0]), 1, val.ptr))
+    T.fill_arrays(e, tree._adv)
+    before = dict(tree.fetch(), **tree._adv.fetch())
+    with pytest.raises(_lib.GymChessError) as ei:
+        _lib.check(L.gc_tree_advance(tree._h, mv.ptr, *(b.ptr for b in dev[4]), 1, val.ptr, tree._adv.ptr["kept"],
+                                     tree._adv.ptr["remap"]))
+    assert str(BOUND) in str(ei.value), str(ei.value)
+    now = dict(tree.fetch(), **tree._adv.fetch())
+    assert all(before[k].tobytes() == now[k].tobytes() for k in before)
+    e.synchronize()
+    tree.close()
+
+    # at the bound
+    tree = e.search_tree(1, BOUND, cap=1)
+    ref = A.AdvTree(1, BOUND, 1)
+    T.fill_tree(e, tree)
+    _lib.check(L.gc_tree_reset(tree._h, *(b.ptr for b in dev[0]), 1, val.ptr))
+    ref.reset(*blocks[0], value=np.array([0.375], dtype=np.float32))
+    values = np.array([[0.5], [-0.25], [0.125]], dtype=np.float32)
+    dvals = Dev(e, values)
+    none = np.zeros(1, dtype=np.uint8)
+    for s in range(3):
+        tree.select(1.25, 0.0)
+        d = tree.fetch("path", "depth")
+        ref.select(1.25, 0.0, follow=(d["path"], d["depth"]))
+        _lib.check(L.gc_tree_backup(tree._h, dvals.ptr + 4 * s, zero.ptr, zero.ptr, *(b.ptr for b in dev[1 + s]), 1))
+        ref.backup(values[s], none, none, *blocks[1 + s])
+        ref.same_as(tree.fetch())
+    assert ref.n_nodes[0] == 4
+    T.fill_arrays(e, tree._root)
+    rp = tree.root_policy(greedy=True)
+    picks = rp.fetch("pick")["pick"]
+    assert picks.tolist() == [100]
+    pri = e.priors_buffer(1, cap=1)
+    put_block(e, pri, blocks[4])
+    T.fill_arrays(e, tree._adv)
+    o = tree.advance(rp.pick, pri, value=val.ptr).fetch()
+    kept, remap = ref.advance(picks, *blocks[4], value=np.array([0.375], dtype=np.float32))
+    assert kept.tolist() == [3] and o["kept"].tolist() == [3]
+    assert remap[0, :5].tolist() == [-1, 0, 1, 2, -1] and (o["remap"] == remap).all()
+    ref.same_as(tree.fetch())
+    e.synchronize()
+    tree.close()
+    pri.close()
+    for b in [x for row in dev for x in row] + [zero, val, mv, dvals]:
+        b.close()
+    e.close()

@@ -103,6 +103,10 @@ class RefTree:
     def _decide(self, g, k, c_puct, fpu, dev_slot):
         """the slot taken at node k: the reference's argmax (lowest slot), or the device's after
         the acceptance rule"""
+        if self.n_children[g, k] == 1:  # nothing to score (most of a chain's cost otherwise)
+            assert dev_slot is None or int(dev_slot) == 0, (g, k, dev_slot)
+            self.decisions += 1
+            return 0
         ref = self.scores(g, k, c_puct, fpu)
         best = float(ref.max())
         tol = TOL * max(1.0, float(np.abs(ref).max()))
@@ -284,15 +288,45 @@ def synth_run(G, nodes, cap, rule, seed):
                 reason=reason, sims=sims, pri_cap=pri_cap)
 
 
-def run_reference(G, nodes, cap, rule, seed, c_puct, fpu):
-    """the reference driven alone through a synthetic run"""
+# trees of more than 64 nodes and paths deeper than 64 (the kernels walk nodes and path entries in
+# chunks of 64, one lane each): (G, nodes, cap, rule, seed, c_puct, fpu) on open_run's inputs
+LARGE_CASES = [(5, 200, 7, "wide", 31, 1.25, -0.5),   # four chunks, broad and deep mixed
+               (3, 130, 1, "wide", 21, 1.25, 0.0),    # a chain: depth = n_nodes - 1
+               (5, 130, 65, "wide", 35, 1.25, -1.0)]  # two slot chunks x three node chunks
+# (the seeds are chosen by test_large_runs_reach_the_later_chunks and test_tree_advance's
+# test_large_runs_cross_the_chunks: the last case's first candidate, 33, drops no node past 64 that
+# has kept nodes after it)
+# the search-only runs: once the chain is full every simulation walks all of it and the
+# reference's cost grows with nodes squared, so there it is 70 nodes long
+LARGE_SEARCH_CASES = [LARGE_CASES[0], (3, 70, 1, "wide", 21, 1.25, 0.0), LARGE_CASES[2]]
+
+
+def open_run(G, nodes, cap, rule, seed):
+    """synth_run without dead ends below the root (its terminal and childless expansions absorb
+    most simulations of a run of more than 100 nodes, and the trees stop growing): no simulation
+    block is done, and every row with count < 1 becomes the one-move list (7, prior 1); the root
+    block stays, childless root of game 3 included"""
     inp = synth_run(G, nodes, cap, rule, seed)
+    inp["done"][:] = 0
+    inp["reason"][:] = 0
+    dead = inp["count"] < 1
+    inp["count"][dead] = 1
+    inp["actions"][dead, 0] = 7
+    inp["priors"][dead, 0] = 1.0
+    return inp
+
+
+def run_reference(G, nodes, cap, rule, seed, c_puct, fpu, make=None):
+    """the reference driven alone through a synthetic run (make: synth_run, or open_run)"""
+    inp = (make or synth_run)(G, nodes, cap, rule, seed)
     t = RefTree(G, nodes, cap)
     t.reset(*inp["root"], value=inp["root_value"])
     inp["ended_at_root"] = np.zeros(G, dtype=np.int64)  # simulations whose path is empty
+    inp["max_depth"] = 0  # the longest path of the run
     for s in range(inp["sims"]):
         t.select(c_puct, fpu)
         inp["ended_at_root"] += t.depth == 0
+        inp["max_depth"] = max(inp["max_depth"], int(t.depth.max()))
         t.backup(inp["value"][s], inp["done"][s], inp["reason"][s], inp["actions"][s], inp["priors"][s],
                  inp["count"][s])
     return t, inp
@@ -408,6 +442,25 @@ def test_near_ties_are_rare(case):
     t, _ = run_reference(*case)
     assert t.decisions > 100
     assert t.near_ties < 0.01 * t.decisions, (t.near_ties, t.decisions)
+
+
+@pytest.mark.parametrize("case", LARGE_SEARCH_CASES, ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}")
+def test_large_runs_reach_the_later_chunks(case):
+    """what makes the GPU test over LARGE_SEARCH_CASES meaningful, on the reference alone: the
+    trees fill (so nodes past the first 64 exist and are walked) and overflow, near-ties stay
+    under the acceptance rule's cap, and the chain's paths are longer than 64 entries -- nodes - 1
+    by construction: at cap 1 with no dead end every game fills (but game 3 of a G > 3 run, whose
+    root is childless).  Another seed has to meet the same conditions."""
+    G, nodes, cap = case[:3]
+    t, inp = run_reference(*case, make=open_run)
+    assert nodes > 64
+    assert not inp["done"].any() and not inp["reason"].any() and (inp["count"] >= 1).all()
+    assert t.overflow.sum() > 0 and (t.n_nodes == nodes).any()
+    assert t.decisions > 100
+    assert t.near_ties < 0.01 * t.decisions, (t.near_ties, t.decisions)
+    if cap == 1:
+        assert (t.n_nodes == nodes).all()
+        assert inp["max_depth"] == nodes - 1 and inp["max_depth"] >= 65
 
 
 def test_acceptance_rule_is_not_vacuous():

@@ -1,6 +1,6 @@
 """GPU: the device search tree (gc_tree_* / BatchedChessEnv.search_tree) against RefTree and the
 acceptance rule of test_tree_search.py: synthetic trees that fill and overflow at every cap that
-takes another path, placement, the root's policy, the full chess loop under both rule sets, and
+takes another path, trees of more than 64 nodes with paths of more than 64 entries, placement, the root's policy, the full chess loop under both rule sets, and
 the state and argument errors.  Buffers come from gc_device_alloc / gc_env_copy; no torch."""
 import ctypes
 
@@ -67,6 +67,7 @@ class Run:
         sel = self.tree.select(self.c_puct, self.fpu)
         if check:
             d = self.tree.fetch("path", "depth")
+            self.depth = d["depth"]  # (the device's, of this selection)
             want = self.ref.select(self.c_puct, self.fpu, follow=(d["path"], d["depth"]))
             o = sel.fetch()
             for got, w, name in zip((o["parent"], o["child"], o["action"]), want, ("parent", "child", "action")):
@@ -111,11 +112,42 @@ def test_synthetic_trees(env, case):
     r.close()
 
 
+@pytest.fixture(scope="module")
+def large_env():
+    """boards for the trees of R.LARGE_CASES (5 x 200 nodes)"""
+    from gym_chess_amd.env import BatchedChessEnv
+
+    e = BatchedChessEnv(1000, device=0, seed=3)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("case", R.LARGE_SEARCH_CASES, ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}")
+def test_large_synthetic_trees(large_env, case):
+    """test_synthetic_trees on trees of more than 64 nodes (R.open_run's inputs, which keep such
+    trees growing): the same checks after every selection and every backup.  The chain's paths
+    grow past 64 entries, so k_tree_backup's lanes take a second path entry each and all of them
+    are compared bit for bit (edge_visits, edge_value)."""
+    G, nodes, cap, rule, seed, c_puct, fpu = case
+    r = Run(large_env, G, nodes, cap, R.open_run(G, nodes, cap, rule, seed), c_puct, fpu)
+    r.reset()
+    deepest = 0
+    for s in range(r.inp["sims"]):
+        r.simulate(s)
+        deepest = max(deepest, int(r.depth.max()))
+    assert r.ref.overflow.sum() > 0 and (r.ref.n_nodes == nodes).any()
+    assert r.ref.near_ties < 0.01 * r.ref.decisions, (r.ref.near_ties, r.ref.decisions)
+    if cap == 1:
+        assert deepest >= 65, deepest
+    r.close()
+
+
 # --------------------------------------------------------------------------- 2. placement
-def _game0(inp):
-    one = {k: np.ascontiguousarray(inp[k][:, :1]) for k in ("actions", "priors", "count", "value", "done", "reason")}
-    one["root"] = tuple(np.ascontiguousarray(a[:1]) for a in inp["root"])
-    one["root_value"] = inp["root_value"][:1].copy()
+def _game0(inp, g=0):
+    """the inputs of game g alone"""
+    one = {k: np.ascontiguousarray(inp[k][:, g: g + 1]) for k in ("actions", "priors", "count", "value", "done", "reason")}
+    one["root"] = tuple(np.ascontiguousarray(a[g: g + 1]) for a in inp["root"])
+    one["root_value"] = inp["root_value"][g: g + 1].copy()
     one["pri_cap"], one["sims"] = inp["pri_cap"], inp["sims"]
     return one
 
