@@ -1,5 +1,5 @@
 // gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation (and
-// advance's remap scratch, allocated when first needed) and the launches of gc_tree.h's kernels,
+// advance's remap scratch and the batch scratch, allocated when first needed) and the launches of gc_tree.h's kernels,
 // all asynchronous on the tree env's stream.
 #pragma once
 
@@ -11,6 +11,11 @@ struct gc_tree {
     size_t bytes = 0;         // the slab, plus the remap scratch once it exists
     int32_t* remap = nullptr;  // [games][nodes]: gc_tree_advance's remap when the caller passes none
     bool pending = false;  // a selection waits for its backup
+    // gc_tree_batch_reserve's scratch: one allocation, GC_TREE_BATCH_ARRAYS arrays in the header's order
+    TreeBatchDev b{};
+    uint8_t* bslab = nullptr;
+    size_t bbytes = 0;
+    int batch_pending = 0;  // leaves per game of the batch that waits for its backup, 0 = none
 };
 
 // the arrays' sizes in bytes, in the header's order
@@ -27,6 +32,12 @@ static void tree_addresses(const gc_tree* t, void* out[GC_TREE_ARRAYS]) {
                                d.depth,   d.leaf,     d.leaf_new,    d.path};
     for (int k = 0; k < GC_TREE_ARRAYS; k++) out[k] = p[k];
 }
+// the batch scratch's sizes in bytes, in the header's order
+static void tree_batch_sizes(size_t G, size_t nodes, size_t cap, size_t K, size_t out[GC_TREE_BATCH_ARRAYS]) {
+    const size_t s[GC_TREE_BATCH_ARRAYS] = {G * nodes * cap, 8 * G * K * nodes, 4 * G * K, 4 * G * K, 4 * G * K, 4 * G};
+    for (int k = 0; k < GC_TREE_BATCH_ARRAYS; k++) out[k] = s[k];
+}
+static const char* const TREE_BATCH_PENDING = "a batch is pending: gc_tree_backup_batch first";
 static inline dim3 tree_grid(const gc_tree* t) { return dim3((unsigned)((t->d.games + TREE_WAVES - 1) / TREE_WAVES)); }
 
 extern "C" int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out) {
@@ -86,6 +97,7 @@ extern "C" int gc_tree_destroy(gc_tree* t) {
     (void)hipSetDevice(t->device);  // (not through e: the env may be gone already)
     if (t->slab) (void)hipFree(t->slab);  // (waits for the device: no launch still uses the arrays)
     if (t->remap) (void)hipFree(t->remap);
+    if (t->bslab) (void)hipFree(t->bslab);
     delete t;
     return 0;
 }
@@ -97,10 +109,15 @@ extern "C" int gc_tree_reset(gc_tree* t, const uint16_t* d_actions, const float*
     if (pri_cap < 1) return fail("pri_cap must be >= 1");
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
+    if (t->batch_pending) {  // the pending descents' marks: no batch pending means every in-flight byte is 0
+        const TreeDev& d = t->d;
+        HIPCHK(hipMemsetAsync(t->b.inflight, 0, (size_t)d.games * d.nodes * d.cap, t->e->stream));
+    }
     const TreePriors p{d_actions, d_priors, d_count, pri_cap};
     k_tree_reset<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, p, d_value);
     HIPCHK(hipGetLastError());
     t->pending = false;
+    t->batch_pending = 0;
     return 0;
 }
 
@@ -111,6 +128,7 @@ extern "C" int gc_tree_select(gc_tree* t, float c_puct, float fpu, int32_t* d_pa
     if (!std::isfinite(c_puct) || c_puct < 0.f) return fail("c_puct must be finite and >= 0");
     if (fpu != fpu) return fail("fpu is NaN");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
     k_tree_select<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent, d_child,
@@ -126,6 +144,7 @@ extern "C" int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d
     if (!d_value || !d_done || !d_reason) return fail("null value / done / reason array");
     if (!d_actions || !d_priors || !d_count) return fail("null priors block");
     if (pri_cap < 1) return fail("pri_cap must be >= 1");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     if (!t->pending) return fail("no selection is pending: gc_tree_select first");
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
@@ -144,6 +163,7 @@ extern "C" int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_
     if (!d_actions || !d_priors || !d_count) return fail("null priors block");
     if (pri_cap < 1) return fail("pri_cap must be >= 1");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     gc_env* e = t->e;
     // the board move is a clone within the tree env: refused where gc_env_clone_boards(e, e, ...) is
     if (e->d.ic.spill.ent)
@@ -186,6 +206,7 @@ extern "C" int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int
     if (!t) return fail("null tree");
     if (flags & ~1) return fail("flags: bit 0 = greedy; every other bit 0");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
     TreeRootArgs a;
@@ -208,6 +229,96 @@ extern "C" int gc_tree_pointers(gc_tree* t, void** out, int n) {
     void* p[GC_TREE_ARRAYS];
     tree_addresses(t, p);
     for (int k = 0; k < n && k < GC_TREE_ARRAYS; k++) out[k] = p[k];
+    return 0;
+}
+
+extern "C" int gc_tree_batch_reserve(gc_tree* t, int max_leaves) {
+    if (!t) return fail("null tree");
+    if (max_leaves < 1 || max_leaves > 64) return fail("max_leaves must be in [1, 64]");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
+    if (t->bslab && t->b.K == max_leaves) return 0;
+    gc_env* e = t->e;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    const TreeDev& d = t->d;
+    size_t sz[GC_TREE_BATCH_ARRAYS], off[GC_TREE_BATCH_ARRAYS], total = 0;
+    tree_batch_sizes((size_t)d.games, (size_t)d.nodes, (size_t)d.cap, (size_t)max_leaves, sz);
+    for (int k = 0; k < GC_TREE_BATCH_ARRAYS; k++) {
+        off[k] = total;
+        total += (sz[k] + 255) & ~(size_t)255;
+    }
+    uint8_t* slab = nullptr;
+    if (dalloc(&slab, total)) return -1;
+    hipError_t rc = hipMemsetAsync(slab, 0, total, e->stream);
+    if (rc != hipSuccess) {
+        (void)hipFree(slab);
+        return fail(std::string("hipMemsetAsync: ") + hipGetErrorString(rc));
+    }
+    if (t->bslab) {
+        (void)hipFree(t->bslab);  // (waits for the device: no launch still uses the old scratch)
+        t->bytes -= t->bbytes;
+    }
+    t->bslab = slab;
+    t->bbytes = total;
+    t->bytes += total;
+    TreeBatchDev& b = t->b;
+    b.inflight = slab + off[0];
+    b.path = (int32_t*)(slab + off[1]);
+    b.depth = (int32_t*)(slab + off[2]);
+    b.leaf = (int32_t*)(slab + off[3]);
+    b.kind = (int32_t*)(slab + off[4]);
+    b.collisions = (int32_t*)(slab + off[5]);
+    b.K = max_leaves;
+    return 0;
+}
+
+extern "C" int gc_tree_select_batch(gc_tree* t, int leaves, float c_puct, float fpu, float vloss, int32_t* d_parent,
+                                    int32_t* d_child, uint16_t* d_action) {
+    if (!t) return fail("null tree");
+    if (!d_parent || !d_child || !d_action) return fail("null output array");
+    if (!t->bslab) return fail("no batch scratch: gc_tree_batch_reserve first");
+    if (leaves < 1 || leaves > t->b.K) return fail("leaves must be in [1, the reserved max_leaves]");
+    if (!std::isfinite(c_puct) || c_puct < 0.f) return fail("c_puct must be finite and >= 0");
+    if (fpu != fpu) return fail("fpu is NaN");
+    if (!std::isfinite(vloss) || vloss < 0.f) return fail("vloss must be finite and >= 0");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    k_tree_select_batch<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->b, leaves, c_puct, fpu, vloss,
+                                                                                  d_parent, d_child, d_action);
+    HIPCHK(hipGetLastError());
+    t->batch_pending = leaves;
+    return 0;
+}
+
+extern "C" int gc_tree_backup_batch(gc_tree* t, const float* d_value, const uint8_t* d_done, const uint8_t* d_reason,
+                                    const uint16_t* d_actions, const float* d_priors, const int32_t* d_count,
+                                    int pri_cap) {
+    if (!t) return fail("null tree");
+    if (!d_value || !d_done || !d_reason) return fail("null value / done / reason array");
+    if (!d_actions || !d_priors || !d_count) return fail("null priors block");
+    if (pri_cap < 1) return fail("pri_cap must be >= 1");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (!t->batch_pending) return fail("no batch is pending: gc_tree_select_batch first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    const TreePriors p{d_actions, d_priors, d_count, pri_cap};
+    k_tree_backup_batch<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->b, t->batch_pending, d_value,
+                                                                                  d_done, d_reason, p);
+    HIPCHK(hipGetLastError());
+    t->batch_pending = 0;
+    return 0;
+}
+
+extern "C" int gc_tree_batch_pointers(gc_tree* t, void** out, int n) {
+    if (!t || !out) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1");
+    if (!t->bslab) return fail("no batch scratch: gc_tree_batch_reserve first");
+    const TreeBatchDev& b = t->b;
+    void* p[GC_TREE_BATCH_ARRAYS] = {b.inflight, b.path, b.depth, b.leaf, b.kind, b.collisions};
+    for (int k = 0; k < n && k < GC_TREE_BATCH_ARRAYS; k++) out[k] = p[k];
     return 0;
 }
 

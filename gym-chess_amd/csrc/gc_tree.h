@@ -1,8 +1,9 @@
 // gc_tree.h -- the batched search tree on the device: per-game node arrays in HBM, a PUCT descent
 // to one leaf per game (k_tree_select), the leaf's expansion and the negamax backup
-// (k_tree_backup), the root's visit distribution with a move (k_tree_root_policy), and the played
-// move's subtree kept across moves (k_tree_advance_mark / k_tree_advance_compact, at the end)
-// (gc_tree_*, include/gymchess.h).
+// (k_tree_backup), the same for several leaves per game per call with a virtual loss
+// (k_tree_select_batch / k_tree_backup_batch), the root's visit distribution with a move
+// (k_tree_root_policy), and the played move's subtree kept across moves (k_tree_advance_mark /
+// k_tree_advance_compact, at the end) (gc_tree_*, include/gymchess.h).
 //
 // Geometry: G games, `nodes` nodes per game, `cap` child slots per node (1..256).  Node k of game
 // g is board g * nodes + k of the tree env; node 0 is the root.  Edge statistics live with the
@@ -270,6 +271,215 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup(const TreeDev T
         const size_t e = (gb + k) * T.cap + j;
         T.edge_visits[e] += 1;
         T.edge_value[e] += ((D - d) & 1) ? -v : v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Several leaves per game per call, with virtual loss (gc_tree_select_batch / gc_tree_backup_batch;
+// the header's contract has the rule and the four ways a descent ends).  The scratch of
+// gc_tree_batch_reserve, K = the reserved leaves per game:
+struct TreeBatchDev {
+    uint8_t* inflight;    // [G][nodes][cap]: descents of the pending batch that hold this edge
+    int32_t* path;        // [G][K][nodes][2]
+    int32_t* depth;       // [G][K]
+    int32_t* leaf;        // [G][K]
+    int32_t* kind;        // [G][K]: 0 an existing node, 1 a new node, 2 a collision
+    int32_t* collisions;  // [G]
+    int K;
+};
+
+// The descents l = 0 .. leaves - 1 of a game run one after another inside the game's wave.  The
+// only value a descent leaves for a later one of the same launch is inflight[k][j], and it never
+// crosses lanes through memory: the lane that owns slot j (j & 63) stores the incremented byte and
+// the same lane is the one that loads it in a later descent, so that lane's own program order is
+// the ordering -- no fence.  Whether the chosen edge was in flight comes out of its owner's
+// register by a shuffle, like the child and the action.  n_nodes, overflow and collisions live in
+// registers for the whole batch and are stored once at the end; a node allotted in this batch is
+// never entered by a later descent, because its parent's child[j] stays -1 until the backup.
+// For cap <= 64 a level is still one round trip: inflight's row joins the loads issued together.
+// With every inflight byte 0 the score is k_tree_select's bit for bit (val - vloss * 0 == val,
+// contracted or not).
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select_batch(const TreeDev T, const TreeBatchDev B,
+                                                                        int leaves, float c_puct, float fpu,
+                                                                        float vloss, int32_t* __restrict__ out_parent,
+                                                                        int32_t* __restrict__ out_child,
+                                                                        uint16_t* __restrict__ out_action) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const float ninf = -__builtin_inff();
+    const size_t gb = (size_t)g * T.nodes;
+    int nn = __builtin_amdgcn_readfirstlane(T.n_nodes[g]);
+    int over = 0, coll = 0;
+    for (int l = 0; l < leaves; l++) {
+        int32_t* path = B.path + ((size_t)g * B.K + l) * T.nodes * 2;
+        int k = 0, D = 0, leaf = 0, kind = 0;
+        int o_parent = -1, o_child = -1;
+        u32 o_action = TREE_NO_ACTION;
+        while (D < T.nodes) {
+            const size_t o = (gb + k) * T.cap;
+            // chunk 0 of the node's rows, its in-flight row and its child count: one round trip
+            const bool in0 = lane < T.cap;
+            int nc = __builtin_amdgcn_readfirstlane(T.n_children[gb + k]);
+            nc = nc < T.cap ? nc : T.cap;
+            int ev0 = in0 ? T.edge_visits[o + lane] : 0;
+            int if0 = in0 ? (int)B.inflight[o + lane] : 0;
+            const float val0 = in0 ? T.edge_value[o + lane] : 0.f;
+            const float pr0 = in0 ? T.prior[o + lane] : 0.f;
+            const int ch0 = in0 ? T.child[o + lane] : -1;
+            const u32 ac0 = in0 ? T.action[o + lane] : TREE_NO_ACTION;
+            if (nc <= 0) break;  // (b) a terminal or childless node: the path ends here
+            if (lane >= nc) ev0 = if0 = 0;
+            const int chunks = (nc + 63) >> 6;
+            int total = ev0 + if0;
+            for (int c = 1; c < chunks; c++) {
+                const int s = c * 64 + lane;
+                total += s < nc ? T.edge_visits[o + s] + (int)B.inflight[o + s] : 0;
+            }
+            total = tree_wave_sum(total);
+            const float sq = sqrtf((float)(1 + total));
+            auto score = [&](int ev, int f, float val, float pr) {
+                const int n = ev + f;
+                const float q = n ? (val - vloss * (float)f) / (float)n : fpu;
+                return q + c_puct * pr * sq / (float)(1 + n);
+            };
+            float best = ninf;
+            int j = -1;
+            {
+                const bool on = lane < nc;
+                const float sc = on ? score(ev0, if0, val0, pr0) : ninf;
+                const float mx = pol_wave_max(sc);
+                const unsigned long long hit = __ballot(on && sc == mx);
+                if (hit) {
+                    best = mx;
+                    j = (int)__builtin_ctzll(hit);
+                }
+            }
+            for (int c = 1; c < chunks; c++) {
+                const int s = c * 64 + lane;
+                const bool on = s < nc;
+                const float sc =
+                    on ? score(T.edge_visits[o + s], (int)B.inflight[o + s], T.edge_value[o + s], T.prior[o + s]) : ninf;
+                const float mx = pol_wave_max(sc);
+                const unsigned long long hit = __ballot(on && sc == mx);
+                if (hit && (j < 0 || mx > best)) {  // an earlier chunk keeps a tie
+                    best = mx;
+                    j = c * 64 + (int)__builtin_ctzll(hit);
+                }
+            }
+            if (j < 0) j = 0;  // (only with NaN scores: some slot, in bounds)
+            // the chosen slot's child, action and in-flight count from the lane that owns the slot
+            const bool mine = lane == (j & 63);
+            int ch, fj;
+            u32 ac;
+            if (j < 64) {
+                ch = ch0, ac = ac0, fj = if0;
+            } else {
+                ch = mine ? T.child[o + j] : -1;
+                ac = mine ? (u32)T.action[o + j] : TREE_NO_ACTION;
+                fj = mine ? (int)B.inflight[o + j] : 0;
+            }
+            ch = __builtin_amdgcn_readfirstlane(__shfl(ch, j & 63, 64));
+            ac = __builtin_amdgcn_readfirstlane(__shfl(ac, j & 63, 64));
+            fj = __builtin_amdgcn_readfirstlane(__shfl(fj, j & 63, 64));
+            if (lane == 0) {
+                path[2 * D] = k;
+                path[2 * D + 1] = j;
+            }
+            const bool down = ch >= 0 && ch < T.nodes;
+            if (!down && fj == 0 && nn >= T.nodes) {  // (c) the game's tree is full: the path ends at k, no mark
+                leaf = k;
+                over++;
+                k = -1;
+                break;
+            }
+            if (mine) B.inflight[o + j] = (uint8_t)(fj + 1);
+            D++;
+            if (down) {  // descend
+                k = ch;
+                continue;
+            }
+            if (fj > 0) {  // (d) an earlier descent of this batch holds the edge
+                leaf = k;
+                kind = 2;
+                coll++;
+            } else {  // (a) a new leaf
+                leaf = nn;
+                kind = 1;
+                o_parent = (int)(gb + k);
+                o_child = (int)(gb + nn);
+                o_action = ac;
+                nn++;
+            }
+            k = -1;
+            break;
+        }
+        if (k >= 0) leaf = k;  // (b)
+        if (lane == 0) {
+            const size_t r = (size_t)g * B.K + l, w = (size_t)g * leaves + l;
+            B.depth[r] = D;
+            B.leaf[r] = leaf;
+            B.kind[r] = kind;
+            out_parent[w] = o_parent;
+            out_child[w] = o_child;
+            out_action[w] = (uint16_t)o_action;
+        }
+    }
+    if (lane == 0) {
+        T.n_nodes[g] = nn;
+        if (over) T.overflow[g] += over;
+        if (coll) B.collisions[g] += coll;
+    }
+}
+
+// The batch's new nodes created and every descent's value added along its path, l ascending: one
+// fp32 add per edge per descent, no atomics, in a fixed order.  An edge sits at the same depth d in
+// every path that contains it (the tree path from the root to its node is unique), so lane d & 63
+// owns it in every descent: with l on the outside and the lanes over d on the inside, the
+// read-modify-writes of one edge -- edge_visits, edge_value and the in-flight byte -- are all one
+// lane's, in that lane's program order; no fence.  A descent's value stays in a register (a new
+// node's leaf_value is stored, never read back here), and a new node's rows are no path entry of
+// this batch, so creating node l inside the loop over l orders nothing.
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup_batch(const TreeDev T, const TreeBatchDev B,
+                                                                        int leaves, const float* __restrict__ value,
+                                                                        const uint8_t* __restrict__ done,
+                                                                        const uint8_t* __restrict__ reason,
+                                                                        const TreePriors P) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const size_t gb = (size_t)g * T.nodes;
+    for (int l = 0; l < leaves; l++) {
+        const size_t r = (size_t)g * B.K + l, w = (size_t)g * leaves + l;
+        const int D = B.depth[r], L = B.leaf[r], kind = B.kind[r];
+        const int32_t* path = B.path + r * T.nodes * 2;
+        if (D < 0 || D > T.nodes || L < 0 || L >= T.nodes) continue;  // (never with a batch pending)
+        float v = 0.f;
+        if (kind == 1) {
+            const bool fin = done[w] != 0;
+            v = fin ? (reason[w] == 1 ? -1.0f : 0.0f) : value[w];  // reason 1: the side to move at L is mated
+            // row w of the block, seen as row g by tree_init_node
+            const size_t sh = w - (size_t)g;
+            const TreePriors Pw{P.actions + sh * P.pri_cap, P.priors + sh * P.pri_cap, P.count + sh, P.pri_cap};
+            tree_init_node(T, g, L, Pw, !fin, lane);
+            if (lane == 0 && D > 0) {
+                const int pk = path[2 * (D - 1)], pj = path[2 * (D - 1) + 1];
+                T.parent[gb + L] = pk;
+                T.parent_slot[gb + L] = pj;
+                T.leaf_value[gb + L] = v;
+                T.terminal[gb + L] = fin ? 1 : 0;
+                if ((unsigned)pk < (unsigned)T.nodes && (unsigned)pj < (unsigned)T.cap) T.child[(gb + pk) * T.cap + pj] = L;
+            }
+        } else if (kind != 2) {
+            v = T.leaf_value[gb + L];  // (a node of an earlier launch)
+        }
+        for (int d = lane; d < D; d += 64) {
+            const int k = path[2 * d], j = path[2 * d + 1];
+            if ((unsigned)k >= (unsigned)T.nodes || (unsigned)j >= (unsigned)T.cap) continue;
+            const size_t e = (gb + k) * T.cap + j;
+            B.inflight[e] -= 1;
+            if (kind == 2) continue;
+            T.edge_visits[e] += 1;
+            T.edge_value[e] += ((D - d) & 1) ? -v : v;
+        }
     }
 }
 

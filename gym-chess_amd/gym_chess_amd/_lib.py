@@ -100,6 +100,10 @@ SIGNATURES = {
     "gc_tree_root_policy": (_I, [_P, _U64, ctypes.c_uint32, _I, _P, _P, _P, _P, _P]),
     "gc_tree_advance": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "gc_tree_pointers": (_I, [_P, _P, _I]),
+    "gc_tree_batch_reserve": (_I, [_P, _I]),
+    "gc_tree_select_batch": (_I, [_P, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
+    "gc_tree_backup_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
+    "gc_tree_batch_pointers": (_I, [_P, _P, _I]),
     "gc_tree_device_bytes": (_U64, [_P]),
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),

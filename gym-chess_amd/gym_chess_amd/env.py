@@ -894,12 +894,27 @@ class SearchTree:
                                      a game without one starts afresh from pri's row g;
                                      adv.kept / adv.remap are device pointers (int32[G], int32[G][nodes])
 
-    ptr[...] are the device addresses of the tree's arrays (ARRAYS), fetch(*keys) host copies."""
+    Several leaves per game per round, steered apart by a virtual loss (gc_tree_select_batch /
+    gc_tree_backup_batch; row g * leaves + l belongs to descent l of game g):
+
+        reserve_batch(max_leaves)    the scratch for up to max_leaves (1..64) leaves per game
+        sel = select_batch(leaves, c_puct, fpu, vloss)   `leaves` descents per game in one launch;
+                                     sel.parent / sel.child / sel.action hold G * leaves rows for
+                                     the env calls (count / rows = G * leaves); a descent that ends
+                                     at an existing node, in a full tree or on an edge an earlier
+                                     descent of the batch holds (a collision) has -1 / -1 / 0xFFFF
+        backup_batch(value, rows, pri)   creates the new nodes and backs every descent up, l
+                                     ascending (value: device float32[G * leaves]; rows / pri:
+                                     buffers of at least G * leaves rows)
+
+    ptr[...] are the device addresses of the tree's arrays (ARRAYS, and BATCH_ARRAYS once
+    reserved), fetch(*keys) host copies (no keys: ARRAYS)."""
 
     ARRAYS = ("action", "prior", "child", "edge_visits", "edge_value", "n_children", "parent", "parent_slot",
               "leaf_value", "terminal", "n_nodes", "overflow", "depth", "leaf", "leaf_new", "path")
+    BATCH_ARRAYS = ("inflight", "b_path", "b_depth", "b_leaf", "b_kind", "collisions")
     _DTYPES = {"action": np.uint16, "prior": np.float32, "edge_value": np.float32, "leaf_value": np.float32,
-               "terminal": np.uint8}
+               "terminal": np.uint8, "inflight": np.uint8}
 
     def __init__(self, env, games, nodes, cap=64):
         self.env, self.games, self.nodes, self.cap = env, int(games), int(nodes), int(cap)
@@ -919,9 +934,15 @@ class SearchTree:
                                          "value": (np.float32, (G,))})
         self._adv = _DeviceArrays(env, {"kept": (np.int32, (G,)), "remap": (np.int32, (G, self.nodes))})
         self._moves = None  # advance()'s staging for uploaded moves, made when first needed
+        self.max_leaves = 0  # reserve_batch()'s size
+        self._bsel = None  # select_batch()'s buffers, games * max_leaves rows
+        self._batch = 0  # leaves per game of the pending batch
 
     def _shape(self, k):
         G, N, C_ = self.games, self.nodes, self.cap
+        if k in self.BATCH_ARRAYS:
+            K = self.max_leaves
+            return {"inflight": (G, N, C_), "b_path": (G, K, N, 2), "collisions": (G,)}.get(k, (G, K))
         if k in ("action", "prior", "child", "edge_visits", "edge_value"):
             return (G, N, C_)
         if k in ("n_children", "parent", "parent_slot", "leaf_value", "terminal"):
@@ -940,6 +961,7 @@ class SearchTree:
         cap)), leaf_value from `value` (a device pointer to float32[G]; None = 0)"""
         a, p, c, pc = self._priors(pri)
         _lib.check(self._L.gc_tree_reset(self._h, a, p, c, pc, int(value) if value else None))
+        self._batch = 0
 
     def select(self, c_puct=1.25, fpu=0.0):
         """the PUCT descent of every game to one leaf; returns the tree's selection buffers
@@ -958,6 +980,56 @@ class SearchTree:
             raise ValueError("value: a device pointer to float32[games]")
         a, p, c, pc = self._priors(pri)
         _lib.check(self._L.gc_tree_backup(self._h, int(value), rows.ptr["done"], rows.ptr["reason"], a, p, c, pc))
+
+    def reserve_batch(self, max_leaves):
+        """the scratch of select_batch / backup_batch for up to max_leaves (1..64) leaves per game
+        (gc_tree_batch_reserve: allocated the first time, again for another size, and only while
+        nothing is pending); its arrays join ptr[...] / fetch()"""
+        K = int(max_leaves)
+        _lib.check(self._L.gc_tree_batch_reserve(self._h, K))
+        addr = (ctypes.c_void_p * len(self.BATCH_ARRAYS))()
+        _lib.check(self._L.gc_tree_batch_pointers(self._h, addr, len(self.BATCH_ARRAYS)))
+        self.ptr.update({k: addr[i] for i, k in enumerate(self.BATCH_ARRAYS)})
+        if K != self.max_leaves:
+            if self._bsel is not None:
+                self.env.synchronize()  # (no env call still reads the old buffers)
+                self._bsel.close()
+            rows = self.games * K
+            self._bsel = _DeviceArrays(self.env, {"parent": (np.int32, (rows,)), "child": (np.int32, (rows,)),
+                                                  "action": (np.uint16, (rows,))})
+            self.max_leaves = K
+
+    def select_batch(self, leaves, c_puct=1.25, fpu=0.0, vloss=1.0):
+        """`leaves` PUCT descents per game in one launch, each seeing the earlier ones' edges as
+        in flight (n_j = visits + in flight, Q_j = (value - vloss * in flight) / n_j); reserves
+        the scratch on first use.  Returns the tree's batch selection buffers: parent / child /
+        action device pointers of games * leaves rows, .fetch()"""
+        leaves = int(leaves)
+        if not self.max_leaves:
+            self.reserve_batch(leaves)
+        s = self._bsel.ptr
+        _lib.check(self._L.gc_tree_select_batch(self._h, leaves, float(c_puct), float(fpu), float(vloss),
+                                                s["parent"], s["child"], s["action"]))
+        self._batch = leaves
+        self._bsel._spec = {k: (dt, (self.games * leaves,)) for k, (dt, _) in self._bsel._spec.items()}
+        return self._bsel
+
+    def backup_batch(self, value, rows, pri):
+        """creates the batch's new nodes and backs every descent up (see the class text)"""
+        if not isinstance(rows, RowsBuffer):
+            raise TypeError("rows must be a rows_buffer()")
+        if not isinstance(pri, PriorsBuffer):
+            raise TypeError("pri must be a priors_buffer()")
+        need = self.games * max(self._batch, 1)
+        if rows.rows < need:
+            raise ValueError(f"the rows buffer holds {rows.rows} rows, the batch {need}")
+        if pri.rows < need:
+            raise ValueError(f"the priors buffer holds {pri.rows} rows, the batch {need}")
+        if not value:
+            raise ValueError("value: a device pointer to float32[games * leaves]")
+        a, p, c, pc = self._priors(pri)
+        _lib.check(self._L.gc_tree_backup_batch(self._h, int(value), rows.ptr["done"], rows.ptr["reason"], a, p, c, pc))
+        self._batch = 0
 
     def root_policy(self, greedy=False, seed=None, draw=0):
         """the roots' actions uint16[G][cap], visits int32[G][cap], pi float32[G][cap], value
@@ -1021,6 +1093,9 @@ class SearchTree:
             self._sel.close()
             self._root.close()
             self._adv.close()
+            if self._bsel is not None:
+                self._bsel.close()
+                self._bsel = None
             if self._moves is not None:
                 self._moves.close()
                 self._moves = None

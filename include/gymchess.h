@@ -342,8 +342,9 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * per game, 1 <= cap <= 256 child slots per node, games * nodes <= gc_env_num_boards(e).  Every
  * call is one launch (gc_tree_advance: three), asynchronous on e's stream (the stream alone orders
  * it against the env calls), and none synchronises the host.  `e` must outlive the tree.
- * Two-player negamax only (an opponent "none" tree env): no rewards along the path, no discount,
- * no virtual loss, one leaf per game per call.
+ * Two-player negamax only (an opponent "none" tree env): no rewards along the path, no discount.
+ * gc_tree_select / gc_tree_backup take one leaf per game per call; gc_tree_select_batch /
+ * gc_tree_backup_batch (below) take several, steered apart by a virtual loss.
  * Arrays (gc_tree_pointers hands out their device addresses in this order; GC_TREE_ARRAYS of them):
  *    0 action      u16 [games][nodes][cap]   a node's child list, action-id order, padding 0xFFFF
  *    1 prior       f32 [games][nodes][cap]   padding 0
@@ -433,8 +434,54 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * or required pointer (all but reset's / advance's d_value, advance's d_remap and root_policy's outputs), games < 1, nodes < 1,
  * cap outside 1..256, games * nodes > gc_env_num_boards(e), pri_cap < 1, a c_puct that is not
  * finite or < 0, a NaN fpu, an unknown flag bit.  gc_tree_pointers writes the first min(n,
- * GC_TREE_ARRAYS) addresses (n >= 1). */
+ * GC_TREE_ARRAYS) addresses (n >= 1).
+ * Several leaves per game per call: gc_tree_select_batch runs the descents l = 0 .. leaves - 1 of
+ * every game one after another in ONE launch, gc_tree_backup_batch backs all of them up in one; row
+ * g * leaves + l of every input and output array belongs to descent l of game g, so a round is
+ * still six launches and each env call gets rows = games * leaves.  The single-leaf calls, their
+ * arrays and gc_tree_pointers are unchanged.
+ * gc_tree_batch_reserve(max_leaves in 1..64) allocates the scratch the first time and reallocates
+ * it when called with another size (the same size: nothing happens); zero-filled on e's stream,
+ * counted by gc_tree_device_bytes.  gc_tree_batch_pointers hands it out in this order
+ * (GC_TREE_BATCH_ARRAYS of them; the first min(n, GC_TREE_BATCH_ARRAYS), n >= 1), K = max_leaves:
+ *    0 inflight    u8  [games][nodes][cap]   descents of the pending batch that hold this edge
+ *    1 b_path      i32 [games][K][nodes][2]  (node, slot) per level, per descent
+ *    2 b_depth     i32 [games][K]            entries of descent l's path
+ *    3 b_leaf      i32 [games][K]            the node its path ends at
+ *    4 b_kind      i32 [games][K]            0 = ends at an existing node; 1 = a new node; 2 = collision
+ *    5 collisions  i32 [games]               collisions since the scratch was reserved (never
+ *                                            cleared by reset or advance)
+ * Whenever no batch is pending every inflight byte is 0 (so a new node's row needs no
+ * initialisation and advance moves nothing of it); gc_tree_reset during a pending batch clears
+ * inflight with one memset on the stream before its launch, and the batch.
+ * gc_tree_select_batch: at node k, with f_j = inflight[k][j], in fp32 and in this order of
+ * operations: n_j = edge_visits[j] + f_j, n = 1 + sum_j n_j, Q_j = n_j ? (edge_value[j] - vloss *
+ * f_j) / n_j : fpu, score_j = Q_j + c_puct * prior_j * sqrt(n) / (1 + n_j); the largest score wins,
+ * ties go to the lowest slot (with every f_j == 0 this is gc_tree_select's score bit for bit).
+ * (k, j) is appended to descent l's path and inflight[k][j] += 1; with child[j] >= 0 the descent
+ * goes on there.  It ends (a) at child[j] == -1 on an edge that was not in flight, with n_nodes <
+ * nodes: a new node gets the next index (n_nodes grows by one per new node of the batch, in order
+ * of l), outputs as gc_tree_select's, b_kind 1; (b) at a terminal or childless node: outputs -1 /
+ * -1 / 0xFFFF, b_kind 0; (c) at child[j] == -1 on an edge that was not in flight, in a full tree:
+ * overflow[g]++, the last entry is dropped and its mark taken back (the pair stays readable at
+ * b_path[b_depth]), the path ends at k, outputs as (b), b_kind 0; (d) a collision: child[j] == -1
+ * but an earlier descent of this batch holds the edge: outputs as (b), b_kind 2, collisions[g]++,
+ * the path and its marks stay until the backup so that later descents are still pushed elsewhere.
+ * A node allotted in this batch is never entered by a later descent of it: its parent's child[j]
+ * stays -1 until the backup.  The env calls skip a (b) / (c) / (d) row as they skip gc_tree_select's.
+ * gc_tree_backup_batch: per game, every kind-1 node is created from row g * leaves + l exactly as
+ * gc_tree_backup creates its leaf; then for l ascending every entry of descent l's path gets
+ * inflight -= 1 and, unless the kind is 2, edge_visits += 1 and edge_value += (D - d odd ? -v : v),
+ * v = leaf_value[b_leaf]: one fp32 add per edge per descent, no atomics, in a fixed order, so a run
+ * is bit-reproducible.  Rows of kind 0 or 2 are not read.
+ * State: the batch calls fail while a single selection is pending; gc_tree_select, gc_tree_backup,
+ * gc_tree_root_policy, gc_tree_advance, gc_tree_batch_reserve and gc_tree_select_batch fail while
+ * a batch is pending, gc_tree_backup_batch fails without one.  gc_tree_select_batch also fails,
+ * with nothing launched, on leaves outside 1..max_leaves or nothing reserved, a vloss that is not
+ * finite or < 0, gc_tree_select's c_puct / fpu rules and a NULL output; gc_tree_backup_batch on
+ * what gc_tree_backup refuses; gc_tree_batch_pointers with nothing reserved. */
 #define GC_TREE_ARRAYS 16
+#define GC_TREE_BATCH_ARRAYS 6
 typedef struct gc_tree gc_tree;
 int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out);
 int gc_tree_destroy(gc_tree* t);
@@ -448,6 +495,12 @@ int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int flags, uin
 int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_t* d_actions, const float* d_priors,
                     const int32_t* d_count, int pri_cap, const float* d_value, int32_t* d_kept, int32_t* d_remap);
 int gc_tree_pointers(gc_tree* t, void** out, int n);
+int gc_tree_batch_reserve(gc_tree* t, int max_leaves);
+int gc_tree_select_batch(gc_tree* t, int leaves, float c_puct, float fpu, float vloss, int32_t* d_parent,
+                         int32_t* d_child, uint16_t* d_action);
+int gc_tree_backup_batch(gc_tree* t, const float* d_value, const uint8_t* d_done, const uint8_t* d_reason,
+                         const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap);
+int gc_tree_batch_pointers(gc_tree* t, void** out, int n);
 uint64_t gc_tree_device_bytes(gc_tree* t);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d

@@ -29,8 +29,25 @@ re-searching the retained visits; the network's time comes on top).  The tree en
 stand at the start position, whose 3-fold window is empty: the board move copies the per-board
 fields only, a window costs what tools/clone_bench.py measures per pair.
 
+--leaves measures the batched calls (gc_tree_select_batch + gc_tree_backup_batch: K leaves per game
+per call, virtual loss 1) on the same synthetic inputs, for G in {32, 1 024} games and K in {1, 4, 8,
+16}, nodes and cap as above.  Per G, setting and K the trees grow from the root over nodes / K
+calls (nodes descents, as the single-leaf run's nodes simulations) and two windows of calls are
+timed by events on the env's stream, issued without a host synchronisation: early (the calls
+covering descents 8..40, two calls at least) and late (the calls covering the last 48 descents, two
+at least).  us_per_call, us_per_leaf = us_per_call / K, collisions_per_call (per game: the mean over
+the games of the collisions counter's growth across the window, per call) and new_nodes_per_call
+(per game) are recorded, medians of REPS_LEAVES runs after a warm-up.  "single" is the single-leaf
+pair (gc_tree_select + gc_tree_backup) in the same process, on the same env, inputs and geometry,
+windows 8..40 and the last 48 simulations: us_per_sim.  The trees of a window are those each
+search grew by then -- a batch and K single simulations do not expand the same nodes.  Two ratios
+are derived per G, setting and window: k1_over_single (one K = 1 call against one single
+simulation: the same work plus the in-flight traffic) and k8_over_8_single (one K = 8 call against
+eight single simulations).
+
     python tools/tree_bench.py [--games G] [--nodes N] [--out profiles/tree_search.json]
     python tools/tree_bench.py --advance [--out profiles/tree_advance.json]
+    python tools/tree_bench.py --leaves [--out profiles/tree_batch.json]
 """
 import argparse
 import ctypes
@@ -259,6 +276,123 @@ def advance_leg(G, nodes, out_path):
             f.write(line + "\n")
 
 
+# ----------------------------------------------------------------------------- several leaves per call
+LEAVES_GAMES = (32, 1024)
+LEAVES_K = (1, 4, 8, 16)
+REPS_LEAVES = 5
+VLOSS = 1.0
+
+
+def leaves_windows(nodes, K):
+    """the calls that cover descents 8..40 and the last 48 descents, two calls each at least"""
+    calls = nodes // K
+    a = max(1, EARLY[0] // K)
+    n_early, n_late = max(2, (EARLY[1] - EARLY[0]) // K), max(2, LATE_LEN // K)
+    return {"early": (a, a + n_early), "late": (calls - n_late, calls)}
+
+
+def leaves_leg(nodes, out_path):
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    res = {"nodes": nodes, "cap": CAP, "vloss": VLOSS, "reps": REPS_LEAVES, "settings": SETTINGS, "runs": []}
+    for G in LEAVES_GAMES:
+        env = BatchedChessEnv(G * nodes, device=0, seed=11)
+        L = env._L
+        tree = env.search_tree(G, nodes, cap=CAP)
+        sel = tree._sel.ptr
+
+        def upload(a):
+            v = ctypes.c_void_p()
+            _lib.check(L.gc_device_alloc(env.device, ctypes.c_uint64(a.nbytes), ctypes.byref(v)))
+            _lib.check(L.gc_env_copy(env._h, v.value, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+            return v.value
+
+        def timed(rows, calls, wins, d, step, counters):
+            """REPS_LEAVES + 1 runs of `calls` calls from the root; per window the times per call and
+            the counters' growth per call (mean over the games)"""
+            def block(s):
+                return (d["actions"] + 2 * rows * CAP * s, d["priors"] + 4 * rows * CAP * s, d["count"] + 4 * rows * s, CAP)
+
+            starts = {a: w for w, (a, b) in wins.items()}
+            ends = {b: w for w, (a, b) in wins.items()}
+            times = {w: [] for w in wins}
+            grow = {}
+            for rep in range(REPS_LEAVES + 1):  # the first run warms up; the trees are the same every run
+                _lib.check(L.gc_tree_reset(tree._h, *block(calls), None))
+                for s in range(calls):
+                    if s in starts:
+                        env.synchronize()
+                        c0 = tree.fetch(*counters)
+                        env.record_event(4)
+                    step(s, block(s))
+                    if s + 1 in ends:
+                        w = ends[s + 1]
+                        env.record_event(5)
+                        env.synchronize()
+                        a, b = wins[w]
+                        if rep:
+                            times[w].append(env.elapsed_ms(4, 5) * 1e3 / (b - a))
+                        c1 = tree.fetch(*counters)
+                        grow[w] = {k: round(float((c1[k] - c0[k]).mean()) / (b - a), 3) for k in counters}
+            return times, grow
+
+        for name, (c_puct, fpu) in SETTINGS.items():
+            # the single-leaf pair: nodes simulations, the windows of the search measurement
+            d = {k: upload(np.ascontiguousarray(v)) for k, v in make_inputs(G, nodes).items()}
+
+            def single(s, blk):
+                _lib.check(L.gc_tree_select(tree._h, c_puct, fpu, sel["parent"], sel["child"], sel["action"]))
+                _lib.check(L.gc_tree_backup(tree._h, d["value"] + 4 * G * s, d["done"] + G * s, d["reason"] + G * s, *blk))
+
+            times, grow = timed(G, nodes, windows(nodes), d, single, ("n_nodes",))
+            one = {w: {"us_per_sim": round(median(t), 2), "us_per_sim_reps": [round(x, 2) for x in t],
+                       "new_nodes_per_sim": grow[w]["n_nodes"]} for w, t in times.items()}
+            env.synchronize()
+            for ptr in d.values():
+                L.gc_device_free(env.device, ctypes.c_void_p(ptr))
+            run = {"games": G, "setting": name, "windows_single": {w: list(ab) for w, ab in windows(nodes).items()},
+                   "single": one, "batch": {}}
+            for K in LEAVES_K:
+                rows, calls = G * K, nodes // K
+                tree.reserve_batch(K)
+                b = tree._bsel.ptr
+                d = {k: upload(np.ascontiguousarray(v)) for k, v in make_inputs(rows, calls).items()}
+
+                def batch(s, blk):
+                    _lib.check(L.gc_tree_select_batch(tree._h, K, c_puct, fpu, VLOSS, b["parent"], b["child"], b["action"]))
+                    _lib.check(L.gc_tree_backup_batch(tree._h, d["value"] + 4 * rows * s, d["done"] + rows * s,
+                                                      d["reason"] + rows * s, *blk))
+
+                wins = leaves_windows(nodes, K)
+                times, grow = timed(rows, calls, wins, d, batch, ("n_nodes", "collisions"))
+                out = {"calls": calls, "windows": {w: list(ab) for w, ab in wins.items()}}
+                for w, t in times.items():
+                    us = median(t)
+                    out[w] = {"us_per_call": round(us, 2), "us_per_leaf": round(us / K, 2),
+                              "us_per_call_reps": [round(x, 2) for x in t],
+                              "collisions_per_call": grow[w]["collisions"], "new_nodes_per_call": grow[w]["n_nodes"],
+                              "single_us_for_K_sims": round(K * one[w]["us_per_sim"], 2),
+                              "call_over_K_single": round(us / (K * one[w]["us_per_sim"]), 3)}
+                run["batch"][str(K)] = out
+                env.synchronize()
+                for ptr in d.values():
+                    L.gc_device_free(env.device, ctypes.c_void_p(ptr))
+            run["k1_over_single"] = {w: run["batch"]["1"][w]["call_over_K_single"] for w in ("early", "late")}
+            run["k8_over_8_single"] = {w: run["batch"]["8"][w]["call_over_K_single"] for w in ("early", "late")}
+            run["tree_bytes"] = tree.device_bytes()
+            res["runs"].append(run)
+            print(json.dumps(run), flush=True)
+        env.synchronize()
+        tree.close()
+        env.close()
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+
+
 # ----------------------------------------------------------------------------- the device leg
 def main():
     ap = argparse.ArgumentParser()
@@ -267,6 +401,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--advance", action="store_true", help="measure gc_tree_advance (see the module text)")
+    ap.add_argument("--leaves", action="store_true", help="measure the batched calls (see the module text)")
     ap.add_argument("--torch-leg", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     G, nodes = args.games, args.nodes
@@ -276,6 +411,9 @@ def main():
         return
     if args.advance:
         advance_leg(G, nodes, args.out)
+        return
+    if args.leaves:
+        leaves_leg(nodes, args.out)
         return
 
     from gym_chess_amd import _lib
