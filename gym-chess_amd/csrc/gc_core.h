@@ -1668,7 +1668,9 @@ GC_HD int apply_move(Pos& s, bool white_player, int action, int* reward, bool* i
 // piece), branch-free.  Same result as apply_move for such moves: the promotion branch is
 // unreachable (a pawn of the mover never reaches the row lib.rs:703-704 tests), a white king
 // move revokes both white rights, a white rook leaving column 0 / 7 revokes one (Q5).
-GC_HD void apply_legal(Pos& s, bool white, int action, int* reward, bool* irrev) {
+// (occ0, kw, rw: occ_of(s), s.k & s.w, s.r & s.w of the position before the move -- the fused
+// ply has them ready before it learns the action)
+GC_HD void apply_legal_with(Pos& s, bool white, int action, int* reward, bool* irrev, u64 occ0, u64 kw, u64 rw) {
     // castles (lib.rs:740-773) in the same branch-free form: the king's and rook's squares
     // (and the ones between) cleared, king and rook put on their targets in the colour of the
     // castle id; both rights of that colour revoked
@@ -1684,8 +1686,8 @@ GC_HD void apply_legal(Pos& s, bool white, int action, int* reward, bool* irrev)
     int v = 10 * (int)((s.q >> t) & 1) + 5 * (int)((s.r >> t) & 1) + 3 * (int)(((s.b | s.n) >> t) & 1) +
             (int)((s.p >> t) & 1);
     *reward = cs ? 0 : v;
-    *irrev = !cs && (((s.p & fm) != 0) || ((occ_of(s) & tm) != 0));
-    bool wk = (s.k & s.w & fm) != 0, wr = (s.r & s.w & fm) != 0;
+    *irrev = !cs && (((s.p & fm) != 0) || ((occ0 & tm) != 0));
+    bool wk = (kw & fm) != 0, wr = (rw & fm) != 0;
 #define GC_MV(X) s.X = (s.X & clr) | ((s.X & fm) ? tm : 0ull)
     GC_MV(k); GC_MV(q); GC_MV(r); GC_MV(b); GC_MV(n); GC_MV(p); GC_MV(w);
 #undef GC_MV
@@ -1696,6 +1698,9 @@ GC_HD void apply_legal(Pos& s, bool white, int action, int* reward, bool* irrev)
                 ((wr && (f & 7) == 7) ? (u32)M_WKC : 0u);
     clear = cs ? (cw ? (u32)(M_WKC | M_WQC) : (u32)(M_BKC | M_BQC)) : clear;
     s.meta = (s.meta & ~clear) ^ M_WHITE;  // current_player = other (lib.rs:778-780)
+}
+GC_HD void apply_legal(Pos& s, bool white, int action, int* reward, bool* irrev) {
+    apply_legal_with(s, white, action, reward, irrev, occ_of(s), s.k & s.w, s.r & s.w);
 }
 
 // ---- board-only key for 3-fold repetition (chess_v2.py:599-602) -------------------------

@@ -2176,13 +2176,25 @@ using QuadSets = QuadSetsT<QuadLds>;
 // the move sets in phase 3 while Q0 and Q1 settle the outcome (the pick was phase 3's longest
 // chain); a board that resets takes the start position's table pick instead.
 struct QuadPend {
-    bool pending;  // false: `a` is already the action (the launch's first ply)
     bool have;     // the move stood: Q2's pick
-    uint16_t ra;   // else: the table pick
-    __device__ int resolve(const QuadLds& L, int l, int a) const {
-        return !pending ? a : have ? (int)L.pick[l] : (int)ra;
+    uint16_t ra;   // else: the table pick (the launch's first ply: the env's action)
+    __device__ int resolve(const QuadLds& L, int l) const {
+        const int pk = (int)L.pick[l];  // read whether taken or not: one ds_read and a select, no exec region
+        return have ? pk : (int)ra;
     }
 };
+// Q0: what the apply needs of the settled state alone, made at the end of phase 3 and held
+// across barrier D: the meta word with the rights State::new sees, the occupancy
+// (irreversible move), the white kings and rooks (rights revoked)
+struct QuadQ0Pre {
+    u32 meta0;
+    u64 occ, kw, rw;
+};
+__device__ __forceinline__ QuadQ0Pre quad_q0pre(const Pos& s) {
+    QuadQ0Pre q{(s.meta & ~(u32)M_RIGHTS) | eff_rights(s), occ_of(s), s.k & s.w, s.r & s.w};
+    pin(q.meta0); pin(q.occ); pin(q.kw); pin(q.rw);
+    return q;
+}
 
 // One ply of board i for role R of its quad (RoleC<0..3>).  Q0 / Q1: in/out as pair_ply (s, a,
 // d, h, nst); both return the same s and a.  Q2 / Q3: s, a, d, h, nst unused.  oq (Q1, OCC):
@@ -2216,7 +2228,7 @@ struct OccQ {
 template <int R, bool OCC>
 __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l, int i, bool live, Pos& s, int& a,
                                             u32& d, DevHist& h, u32& nst, RepProbe& pr, QuadPend& pend, OccQ& oq,
-                                            bool up = false) {
+                                            QuadQ0Pre& q0, bool up = false) {
     constexpr bool CARRY = R < 2;  // Q0 / Q1 hold the state
 #ifdef GC_PSTAMPS
     bool pst_loaded = false;  // Q1: the commit loaded a slot beyond the home slot
@@ -2226,7 +2238,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     if (R == 2) QSETPRIO(0, up);
     if (GC_WG_FAIR && R == 1) QSETPRIO(2, up);
     if (GC_WG_FAIR && R == 3) QSETPRIO(0, up);
-    if (R == 0) a = pend.resolve(L, l, a);  // the last ply's action: Q2's pick, or the reset table's
+    if (R == 0) a = pend.resolve(L, l);  // the last ply's action: Q2's pick, or the reset table's
     u32 x0 = 0;
     uint16_t ra = (uint16_t)A_NONE;
     if (R == 1) {  // phase 0 work first: it does not depend on the action, which Q1 learns after it
@@ -2251,8 +2263,8 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     // ---- phase 0
     if (R == 0) {
         ns = s;
-        ns.meta = (ns.meta & ~(u32)M_RIGHTS) | eff_rights(s);  // State::new
-        if (mv) apply_legal(ns, white, a, &mr, &irrev);
+        ns.meta = q0.meta0;  // State::new's rights
+        if (mv) apply_legal_with(ns, white, a, &mr, &irrev, q0.occ, q0.kw, q0.rw);
         L.ns[0][l] = ns.k; L.ns[1][l] = ns.q; L.ns[2][l] = ns.r; L.ns[3][l] = ns.b;
         L.ns[4][l] = ns.n; L.ns[5][l] = ns.p; L.ns[6][l] = ns.w;
         L.nmeta[l] = ns.meta;
@@ -2484,7 +2496,10 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         // reset's pick count is its total) and Q0's pending choice of the next action
         const int tot = have ? total : (int)C.rtotal;
         d += tot > 0 ? 1u : 0u;
-        if (R == 0) pend = QuadPend{true, have, ra};
+        if (R == 0) {
+            pend = QuadPend{have, ra};
+            q0 = quad_q0pre(s);  // the next ply's, in the wait for barrier D
+        }
     }
     PST(6);
     pair_barrier();  // Q2's pick to Q0; LDS free for the next ply
@@ -2561,7 +2576,9 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     // empty (from the launch's start, or at a reset / an irreversible move); until then the board
     // is probed in the table
     OccQ oq{RR == 1 && hl_of(s.meta) == 0, RR == 1, true, false};
-    QuadPend pend{false, false, 0};  // Q0: the first ply's action is the env's
+    QuadPend pend{false, (uint16_t)ua};  // Q0: the first ply's action is the env's
+    QuadQ0Pre q0{};
+    if (RR == 0) q0 = quad_q0pre(s);
 #ifdef GC_PSTAMPS
     const unsigned long long g_pst_entry = pst_entry_where();
     unsigned long long rt1 = 0;
@@ -2577,15 +2594,18 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     u32 sa = 0, sb = 0, sc = 0;  // steps | errors << 16, mates | 3-folds << 16, move caps | no-moves << 16
     int32_t rsum = 0;
     StepOut o = {0, 0, R_NONE, 0};
-    for (int p = 0; p < plies; p++) {
-        // (GC_WG_FAIR, above: this workgroup's turn one level up)
 #ifndef GC_TURN_SHIFT
 #define GC_TURN_SHIFT 2  // turns of 4 plies: same box at K = 20, 8 repeats, 13.32 vs 13.01e9 (events
                          // 4.53 vs 4.66 us per ply; 8-ply turns 13.22); at K = 1 000 level (run_r06v, w).
                          // One quad per workgroup, K = 1 000: 17.06 vs 16.87 (2 plies), 16.82e9 (1)
 #endif
-        const bool up = GC_WG_FAIR && roll_turn<QW>(place, p >> GC_TURN_SHIFT);
-        o = quad_ply<RR, OCC>(L, C, l, i, live, s, a, d, h, nst, pr, pend, oq, up);
+    // (GC_WG_FAIR, above: this workgroup's turn one level up; the turn's bit is made once per turn)
+    constexpr int TURN = 1 << GC_TURN_SHIFT;
+    for (int p0 = 0; p0 < plies; p0 += TURN) {
+      const bool up = GC_WG_FAIR && roll_turn<QW>(place, p0 >> GC_TURN_SHIFT);
+      const int pe = p0 + TURN < plies ? p0 + TURN : plies;
+      for (int p = p0; p < pe; p++) {
+        o = quad_ply<RR, OCC>(L, C, l, i, live, s, a, d, h, nst, pr, pend, oq, q0, up);
         const int played = a;  // (Q0: resolved at the ply's start; Q1: read after its barrier A)
 #ifdef GC_PSTAMPS
         if (p == 0) rt1 = __builtin_amdgcn_s_memrealtime();
@@ -2606,6 +2626,7 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
             }
             h.commit();  // this ply's window write lands before the next ply's probe
         }
+      }
     }
 #ifdef GC_PSTAMPS
     if (g_pst_out != nullptr && l == 0) {
@@ -2624,7 +2645,7 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     if (!live || RR >= 2) return;
     const PairIO io = store_io(slab, nn);
     if (RR == 0) {
-        a = pend.resolve(L, l, a);  // the next action (Q2's last pick arrived before the last barrier)
+        a = pend.resolve(L, l);  // the next action (Q2's last pick arrived before the last barrier)
         io.act[i] = (uint16_t)a;
         io.draw[i] = d;
     } else {
