@@ -4730,6 +4730,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_planes.h"
 #include "gc_clone.h"
 #include "gc_tree.h"
+#include "gc_replay.h"
 
 // ----------------------------------------------------------------------------- host side (the C ABI)
 #include "gc_fen.h"
@@ -4741,4 +4742,5 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_host_env.h"
 #include "gc_host_clone.h"
 #include "gc_host_tree.h"
+#include "gc_host_replay.h"
 #include "gc_host_ckpt.h"

@@ -105,6 +105,16 @@ SIGNATURES = {
     "gc_tree_backup_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "gc_tree_batch_pointers": (_I, [_P, _P, _I]),
     "gc_tree_device_bytes": (_U64, [_P]),
+    "gc_replay_create": (_I, [_P, _I, _I, _I, ctypes.c_int64, _P]),
+    "gc_replay_destroy": (_I, [_P]),
+    "gc_replay_clear": (_I, [_P]),
+    "gc_replay_record": (_I, [_P, _P, _P, _I]),
+    "gc_replay_commit": (_I, [_P, _P, _P, _P]),
+    "gc_replay_sample": (_I, [_P, _I, _P, _U64, ctypes.c_uint32, _P, _I, ctypes.c_int64, _I, _P, ctypes.c_int64,
+                              _P, _P, _P, _P]),
+    "gc_replay_counters": (_I, [_P, _P, _P, _P, _P]),
+    "gc_replay_pointers": (_I, [_P, _P, _I]),
+    "gc_replay_device_bytes": (_U64, [_P]),
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),
     "gc_device_free": (_I, [_I, _P]),

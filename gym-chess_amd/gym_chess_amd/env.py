@@ -63,6 +63,11 @@ class BatchedChessEnv:
                 if t is not None:
                     t.close()
             self._trees = []
+            for ref in getattr(self, "_stores", ()):  # sample stores too
+                st = ref()
+                if st is not None:
+                    st.close()
+            self._stores = []
             self._clone_free()
             self._priors_free()
             self._rows_free()
@@ -626,6 +631,18 @@ class BatchedChessEnv:
         self._trees.append(weakref.ref(t))
         return t
 
+    # ------------------------------------------------------------------ training samples
+    def sample_store(self, games=None, cap=64, max_plies=160, capacity=None):
+        """A store of self-play training samples on the device (gc_replay_*): game g is board g of
+        this (game) env; `cap` (action, visits) entries per sample, up to `max_plies` pending
+        samples per game, a ring of `capacity` committed samples (None = 4 * games * max_plies;
+        at least games * max_plies).  See SampleStore."""
+        st = SampleStore(self, games=games, cap=cap, max_plies=max_plies, capacity=capacity)
+        if not hasattr(self, "_stores"):
+            self._stores = []
+        self._stores.append(weakref.ref(st))
+        return st
+
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""
         v = ctypes.c_void_p()
@@ -1099,6 +1116,197 @@ class SearchTree:
             if self._moves is not None:
                 self._moves.close()
                 self._moves = None
+            self.ptr = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SampleStore:
+    """Self-play training samples on the device (gc_replay_*, gym-chess_amd/csrc/gc_replay.h).
+    Every call is asynchronous on the env's stream; the ring's contents are a deterministic
+    function of the call sequence.
+
+        record(root)                 before the move is played: the board's packed position and the
+                                     root's (action, visits) list become the game's next pending
+                                     sample (root: a tree's root_policy() result, or (actions_ptr,
+                                     visits_ptr, row_cap)); games whose visits sum to 0 are skipped
+        commit(io)                   after the step: every finished game's pending samples get z --
+                                     +1 / -1 / 0 from the step's reason (or `outcome`), alternating
+                                     back through the plies on an opponent="none" env, constant on an
+                                     env with an opponent -- and enter the ring (io: the step's
+                                     DeviceIO, or a device pointer to done uint8[G] with reason= /
+                                     outcome= device pointers)
+        batch = sample(rows, ...)    one launch: planes (encode_planes' bytes at record time), the
+                                     policy target in the network's view (dense [rows][4100] and
+                                     sparse index / value [rows][cap]), z and the slot per row;
+                                     slots drawn from the Philox stream (seed, row, draw) over the
+                                     live samples, or given by index=; batch.planes / pi_dense /
+                                     pi_index / pi / z / slot are device pointers, batch.fetch() host
+                                     copies
+        counters()                   waits for the stream: total, live, plies, dropped
+
+    ptr[...] are the device addresses of the store's arrays (ARRAYS), fetch(*keys) host copies."""
+
+    ARRAYS = ("pend_pos", "pend_act", "pend_vis", "ring_pos", "ring_act", "ring_vis", "ring_z", "plies", "dropped",
+              "total", "off", "base")
+    _DTYPES = {"pend_pos": np.uint64, "ring_pos": np.uint64, "pend_act": np.uint16, "ring_act": np.uint16,
+               "ring_z": np.float32, "total": np.uint64, "base": np.uint64}
+    ROW = 4100  # elements of a logits row
+
+    def __init__(self, env, games=None, cap=64, max_plies=160, capacity=None):
+        self.env = env
+        self.games = env.num_boards if games is None else int(games)
+        self.cap, self.max_plies = int(cap), int(max_plies)
+        self.capacity = 4 * self.games * self.max_plies if capacity is None else int(capacity)
+        self._L = env._L
+        self._h = None
+        self._batch = None  # sample()'s own output buffers and their key
+        self._batch_key = None
+        self._index = None  # sample()'s staging for an uploaded index
+        h = ctypes.c_void_p()
+        _lib.check(self._L.gc_replay_create(env._h, self.games, self.cap, self.max_plies,
+                                            ctypes.c_int64(self.capacity), ctypes.byref(h)))
+        self._h = h
+        addr = (ctypes.c_void_p * len(self.ARRAYS))()
+        _lib.check(self._L.gc_replay_pointers(self._h, addr, len(self.ARRAYS)))
+        self.ptr = {k: addr[i] for i, k in enumerate(self.ARRAYS)}
+
+    def _shape(self, k):
+        G, P, C_, R = self.games, self.max_plies, self.cap, self.capacity
+        return {"pend_pos": (G, P, 8), "pend_act": (G, P, C_), "pend_vis": (G, P, C_), "ring_pos": (R, 8),
+                "ring_act": (R, C_), "ring_vis": (R, C_), "ring_z": (R,), "total": (1,), "base": (1,)}.get(k, (G,))
+
+    def record(self, root):
+        """the positions before the move and the roots' visit counts (gc_replay_record)"""
+        if isinstance(root, _DeviceArrays):
+            a, v, rc = root.ptr["actions"], root.ptr["visits"], root._spec["actions"][1][-1]
+        else:
+            a, v, rc = root
+        _lib.check(self._L.gc_replay_record(self._h, int(a), int(v), int(rc)))
+
+    def commit(self, io_or_done, reason=None, outcome=None):
+        """finished games' samples get z and enter the ring (gc_replay_commit): a DeviceIO (its
+        done / reason buffers), or device pointers to done uint8[G] and reason uint8[G];
+        outcome: a device pointer to float32[G], the last recorded position's value from its
+        mover's view, instead of the reason's +1 / -1 / 0"""
+        if isinstance(io_or_done, DeviceIO):
+            done = io_or_done.ptr["done"]
+            reason = io_or_done.ptr["reason"] if reason is None else reason
+        else:
+            done = int(io_or_done)
+        _lib.check(self._L.gc_replay_commit(self._h, done, int(reason) if reason else None,
+                                            int(outcome) if outcome else None))
+
+    def sample(self, rows, seed=None, draw=0, index=None, planes=None, dtype="float16", layout="nchw",
+               perspective=True, dense=True, row_stride=None, pi_stride=None):
+        """A minibatch of `rows` samples in one launch (gc_replay_sample).  index: None = slots drawn
+        from the Philox stream (seed, row, draw) over the live samples (seed None = the env's; the
+        caller advances draw); an array-like of ring slots (uploaded on the env's stream, a
+        synchronous copy) or a device pointer (int) to int32[rows].  planes: None = a buffer of the
+        store's, a planes_buffer(rows=...) or a device pointer; dtype / layout / row_stride as
+        encode_planes_rows, perspective = the side-to-move view of planes AND target.  dense:
+        also the [rows][pi_stride] float32 target (pi_stride None = 4100).  The store's own output
+        buffers are reused by the next sample() of the same shape and freed on another."""
+        env = self.env
+        rows = int(rows)
+        if rows < 0:
+            raise ValueError(f"rows {rows} < 0")
+        buf = planes if isinstance(planes, PlanesBuffer) else None
+        if buf is not None:
+            dtype, layout, row_stride = buf.dtype, buf.layout, buf.board_stride
+            if rows > buf.rows:
+                raise ValueError(f"{rows} rows, the planes buffer holds {buf.rows}")
+        if dtype not in env.POLICY_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(env.POLICY_DTYPES)}, got {dtype!r}")
+        if layout not in env.PLANES_LAYOUTS:
+            raise ValueError(f"layout must be one of {sorted(env.PLANES_LAYOUTS)}, got {layout!r}")
+        row_stride = int(env.PLANES * 64 if row_stride is None else row_stride)
+        pi_stride = int(self.ROW if pi_stride is None else pi_stride)
+        raw = PlanesBuffer._RAW[dtype]
+        key = (rows, dtype, row_stride, planes is None, bool(dense), pi_stride)
+        if key != self._batch_key:
+            self._drop_batch()
+            spec = {"pi_index": (np.int32, (rows, self.cap)), "pi": (np.float32, (rows, self.cap)),
+                    "z": (np.float32, (rows,)), "slot": (np.int32, (rows,))}
+            if planes is None:
+                spec["planes"] = (raw, (rows, row_stride))
+            if dense:
+                spec["pi_dense"] = (np.float32, (rows, pi_stride))
+            self._batch, self._batch_key = _DeviceArrays(env, spec), key
+        b = self._batch
+        if planes is not None:
+            b.ptr["planes"] = buf.ptr if buf is not None else int(planes)
+            b._spec["planes"] = (raw, (rows, row_stride))
+        if index is None:
+            pidx = None
+        elif isinstance(index, int):
+            pidx = index or None
+        else:
+            ix = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+            if ix.size != rows:
+                raise ValueError(f"{ix.size} slots for {rows} rows")
+            ix = np.clip(ix, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
+            if self._index is None or self._index._spec["index"][1][0] < max(rows, 1):
+                if self._index is not None:
+                    env.synchronize()
+                    self._index.close()
+                self._index = _DeviceArrays(env, {"index": (np.int32, (max(rows, 1),))})
+            pidx = self._index.ptr["index"]
+            if rows:
+                _lib.check(self._L.gc_env_copy(env._h, pidx, _lib.ptr(ix), ctypes.c_uint64(ix.nbytes), 1))
+        p = b.ptr
+        _lib.check(self._L.gc_replay_sample(self._h, rows, pidx, ctypes.c_uint64(env.seed if seed is None else int(seed)),
+                                            int(draw) & 0xFFFFFFFF, p["planes"], env.POLICY_DTYPES[dtype],
+                                            ctypes.c_int64(row_stride),
+                                            env.PLANES_LAYOUTS[layout] | int(bool(perspective)), p.get("pi_dense"),
+                                            ctypes.c_int64(pi_stride), p["pi_index"], p["pi"], p["z"], p["slot"]))
+        return b
+
+    def _drop_batch(self):
+        """frees sample()'s own output buffers (never a caller's planes)"""
+        if self._batch is not None:
+            if self._h:
+                self.env.synchronize()  # (no launch still writes them)
+            if not self._batch_key[3]:
+                self._batch.ptr.pop("planes", None)
+            self._batch.close()
+            self._batch, self._batch_key = None, None
+
+    def counters(self):
+        """waits for the env's stream: dict of total (samples ever committed), live (min(total,
+        capacity)), plies (pending records over all games) and dropped (records past max_plies)"""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _lib.check(self._L.gc_replay_counters(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("total", "live", "plies", "dropped"), (int(x.value) for x in v)))
+
+    def clear(self):
+        """everything back to zero, as after creation"""
+        _lib.check(self._L.gc_replay_clear(self._h))
+
+    def fetch(self, *keys):
+        """host copies of the store's arrays (waits for the env's stream)"""
+        out = {}
+        for k in keys or self.ARRAYS:
+            a = np.zeros(self._shape(k), dtype=self._DTYPES.get(k, np.int32))
+            _lib.check(self._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
+            out[k] = a
+        return out
+
+    def device_bytes(self):
+        return int(self._L.gc_replay_device_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gc_replay_destroy(self._h)  # (waits for the device)
+            self._h = None
+            self._drop_batch()
+            if self._index is not None:
+                self._index.close()
+                self._index = None
             self.ptr = {}
 
     def __del__(self):

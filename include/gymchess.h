@@ -502,6 +502,95 @@ int gc_tree_backup_batch(gc_tree* t, const float* d_value, const uint8_t* d_done
                          const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap);
 int gc_tree_batch_pointers(gc_tree* t, void** out, int n);
 uint64_t gc_tree_device_bytes(gc_tree* t);
+/* The sample store (gc_replay.h): self-play training samples kept on the device.  Every move a
+ * packed position and the root's visit counts are recorded per game; when a game ends its samples
+ * get the outcome and enter a ring; a minibatch (planes, policy target in the network's view, value
+ * target) is decoded from ring slots in one launch.  Game g is board g of `e` (normally the GAME
+ * env), which the store only ever reads: either rule set, any opponent mode or colour.  `e` must
+ * outlive the store.  Every call is asynchronous on e's stream, none but gc_replay_counters
+ * synchronises the host, and none uses atomics: the ring is a deterministic function of the call
+ * sequence, and a run is bit-reproducible.
+ * gc_replay_create: 1 <= games <= gc_env_num_boards(e), 1 <= cap <= 256 entries per sample,
+ * max_plies >= 1 pending samples per game, games * max_plies <= capacity < 2^31 ring slots (so one
+ * commit never laps the ring).  One allocation, zeroed on e's stream.
+ * A sample is one row of each of three arrays (the pending area and the ring share the layout):
+ *   pos  u64[8]    the board at record time: bitboards K, Q, R, B, N, P (both colours), WHITE's
+ *                  pieces; word 7 = the env's meta word (bits 0-31: side to move, castle rights,
+ *                  check flags, move_count, the FIDE en-passant file) | the position's count in its
+ *                  live 3-fold window at record time, saturated at 2 (bits 32-39) | n, the number
+ *                  of entries (bits 40-48).  64 bytes.
+ *   act  u16[cap]  the n actions, then 0xFFFF
+ *   vis  i32[cap]  their visit counts, then 0
+ * and, in the ring, z f32: 68 + 6 * cap bytes per committed sample.
+ * Arrays (gc_replay_pointers hands out their device addresses in this order; GC_REPLAY_ARRAYS):
+ *    0 pend_pos u64 [games][max_plies][8]     6 ring_z   f32 [capacity]
+ *    1 pend_act u16 [games][max_plies][cap]   7 plies    i32 [games]  records of the running episode
+ *    2 pend_vis i32 [games][max_plies][cap]   8 dropped  i32 [games]  records past max_plies, ever
+ *    3 ring_pos u64 [capacity][8]             9 total    u64 [1]      samples ever committed
+ *    4 ring_act u16 [capacity][cap]          10 off      i32 [games]  the last commit's prefix (below)
+ *    5 ring_vis i32 [capacity][cap]          11 base     u64 [1]      total before the last commit
+ * gc_replay_record(d_actions, d_visits, row_cap): gc_tree_root_policy's actions / visits blocks,
+ * [games][row_cap], padding 0xFFFF / 0; row_cap <= cap.  A game whose row's visits sum to 0 is
+ * skipped entirely (no move is played from it).  Otherwise, with p = plies[g]: if p < max_plies,
+ * pending sample p of game g is written -- the position from board g's current state (so call it
+ * BEFORE the step that plays the move), the row's entries whose action is not 0xFFFF in row
+ * order, padding behind them, all cap slots defined --; else dropped[g]++.  Either way plies[g]++.
+ * gc_replay_commit(d_done u8[games], d_reason u8[games], d_outcome f32[games] or NULL): a step's
+ * done / reason outputs.  z_last, the value of the last recorded position from the view of the
+ * side that moved there, is d_outcome[g] when given (d_reason may then be NULL), else +1 for
+ * reason 1 (mate), -1 for reason 8 (the agent mated by the opponent's reply), +0.0 for every
+ * other.  For every game with d_done[g] != 0 and P = plies[g] > 0, stored sample p < min(P,
+ * max_plies) gets z = ((P - 1 - p) & 1) ? -z_last : z_last on an opponent "none" env (the sides
+ * alternate; dropped records keep the parity right) and z = z_last on an env with an opponent
+ * inside the step (every sample is the agent's); a zero z_last gives +0.0 throughout.  The
+ * game's stored samples go to ring slots (total + off[g] + p) mod capacity, off = the exclusive
+ * prefix sum, over games in ascending order, of the samples each committing game stores; then
+ * total += their sum and plies[g] = 0 (also for a done game with nothing recorded).  Games that
+ * are not done keep their pending samples.  Two launches: the scan (one workgroup), the copy.
+ * gc_replay_sample: one launch.  live = min(total, capacity), read on the device.  Row j takes
+ * slot d_index[j] (DEVICE int32[rows]) when d_index is given, else slot (uint64(philox_x0(seed, j,
+ * draw)) * live) >> 32, gc_env_sample_policy's Philox stream.  Every output pointer may be NULL.
+ * For a slot in [0, live):
+ *   d_planes     row j (at element j * row_stride, 0 = 24 * 64) = the 24 planes; dtype, row_stride,
+ *                flags (bit 0 side-to-move view, bit 1 channels-last), alignment and contents exactly
+ *                as gc_env_encode_planes_rows, bit for bit what gc_env_encode_planes would have
+ *                written for that board at record time (plane 22 from the meta word under FIDE
+ *                rules -- the rules of `e` at the time of THIS call).
+ *   d_pi_index   i32 [rows][cap], d_pi f32 [rows][cap]: the sparse target.  Entry k < n: the
+ *                logits-row element -- action a, or with flags bit 0 on a position with BLACK to
+ *                move mirror(a) (gc_env_sample_policy's) -- and (float)visits_k / (float)(sum of
+ *                the n visits) (0 when the sum is not positive); padding -1 / 0.  An action >=
+ *                4100 has no logits-row element: index -1, value 0, its visits still in the sum.
+ *   d_pi_dense   f32, row j at element j * pi_stride: the same target scattered into a zero row.
+ *                Every one of the row's 4100 elements is written exactly once, the stride's padding
+ *                never.  pi_stride >= 4100, a multiple of 4; the buffer 16-byte aligned.  (Actions
+ *                of one sample are distinct as gc_tree_root_policy writes them; of duplicates one wins.)
+ *   d_z[j] f32, d_slot[j] i32 = the slot.
+ * A slot outside [0, live) (so every row while live == 0) gives zero planes, an all-padding sparse
+ * and an all-zero dense target, z = 0 and d_slot = -1.  Whatever d_index holds, every access stays
+ * in bounds.
+ * gc_replay_clear: everything back to zero, as after creation (one memset on the stream).
+ * gc_replay_counters: synchronises e's stream; total, live, and the sums over games of plies and
+ * dropped (each output may be NULL).  gc_replay_pointers writes the first min(n, GC_REPLAY_ARRAYS)
+ * addresses (n >= 1).
+ * Every call fails with nothing launched on a NULL handle or required pointer (create: e, out;
+ * record: both blocks; commit: d_done, and d_reason without d_outcome); create on the limits
+ * above; record on row_cap outside 1..cap; sample on rows < 0, an unknown dtype or flag bit, and --
+ * for an output that is given -- row_stride in 1..1535 or no multiple of 8, pi_stride < 4100 or
+ * no multiple of 4, a misaligned buffer.  rows == 0 succeeds and launches nothing. */
+#define GC_REPLAY_ARRAYS 12
+typedef struct gc_replay gc_replay;
+int gc_replay_create(gc_env* e, int games, int cap, int max_plies, int64_t capacity, gc_replay** out);
+int gc_replay_destroy(gc_replay* r);
+int gc_replay_clear(gc_replay* r);
+int gc_replay_record(gc_replay* r, const uint16_t* d_actions, const int32_t* d_visits, int row_cap);
+int gc_replay_commit(gc_replay* r, const uint8_t* d_done, const uint8_t* d_reason, const float* d_outcome);
+int gc_replay_sample(gc_replay* r, int rows, const int32_t* d_index, uint64_t seed, uint32_t draw, void* d_planes,
+                     int dtype, int64_t row_stride, int flags, float* d_pi_dense, int64_t pi_stride,
+                     int32_t* d_pi_index, float* d_pi, float* d_z, int32_t* d_slot);
+int gc_replay_counters(gc_replay* r, uint64_t* total, uint64_t* live, uint64_t* plies, uint64_t* dropped);
+int gc_replay_pointers(gc_replay* r, void** out, int n);
+uint64_t gc_replay_device_bytes(gc_replay* r);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
