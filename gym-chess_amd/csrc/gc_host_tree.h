@@ -1,5 +1,5 @@
 // gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation (and
-// advance's remap scratch and the batch scratch, allocated when first needed) and the launches of gc_tree.h's kernels,
+// advance's remap scratch, the batch scratch and the solver's arrays, allocated when first needed) and the launches of gc_tree.h's kernels,
 // all asynchronous on the tree env's stream.
 #pragma once
 
@@ -16,6 +16,9 @@ struct gc_tree {
     uint8_t* bslab = nullptr;
     size_t bbytes = 0;
     int batch_pending = 0;  // leaves per game of the batch that waits for its backup, 0 = none
+    // gc_tree_solver_enable's arrays: one allocation, GC_TREE_SOLVER_ARRAYS arrays in the header's order
+    TreeSolverDev v{};
+    uint8_t* vslab = nullptr;
 };
 
 // the arrays' sizes in bytes, in the header's order
@@ -37,7 +40,15 @@ static void tree_batch_sizes(size_t G, size_t nodes, size_t cap, size_t K, size_
     const size_t s[GC_TREE_BATCH_ARRAYS] = {G * nodes * cap, 8 * G * K * nodes, 4 * G * K, 4 * G * K, 4 * G * K, 4 * G};
     for (int k = 0; k < GC_TREE_BATCH_ARRAYS; k++) out[k] = s[k];
 }
+// the solver's arrays' sizes in bytes, in the header's order
+static void tree_solver_sizes(size_t G, size_t nodes, size_t cap, size_t out[GC_TREE_SOLVER_ARRAYS]) {
+    const size_t e = G * nodes * cap, n = G * nodes;
+    const size_t s[GC_TREE_SOLVER_ARRAYS] = {e, 2 * e, n, 2 * n, n};
+    for (int k = 0; k < GC_TREE_SOLVER_ARRAYS; k++) out[k] = s[k];
+}
 static const char* const TREE_BATCH_PENDING = "a batch is pending: gc_tree_backup_batch first";
+static const char* const TREE_SOLVER_NO_BATCH =
+    "a solver tree takes one leaf per game per call: the batch calls are not defined for it yet";
 static inline dim3 tree_grid(const gc_tree* t) { return dim3((unsigned)((t->d.games + TREE_WAVES - 1) / TREE_WAVES)); }
 
 extern "C" int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out) {
@@ -98,6 +109,7 @@ extern "C" int gc_tree_destroy(gc_tree* t) {
     if (t->slab) (void)hipFree(t->slab);  // (waits for the device: no launch still uses the arrays)
     if (t->remap) (void)hipFree(t->remap);
     if (t->bslab) (void)hipFree(t->bslab);
+    if (t->vslab) (void)hipFree(t->vslab);
     delete t;
     return 0;
 }
@@ -114,7 +126,10 @@ extern "C" int gc_tree_reset(gc_tree* t, const uint16_t* d_actions, const float*
         HIPCHK(hipMemsetAsync(t->b.inflight, 0, (size_t)d.games * d.nodes * d.cap, t->e->stream));
     }
     const TreePriors p{d_actions, d_priors, d_count, pri_cap};
-    k_tree_reset<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, p, d_value);
+    if (t->vslab)
+        k_tree_reset<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, p, d_value, t->v);
+    else
+        k_tree_reset<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, p, d_value, t->v);
     HIPCHK(hipGetLastError());
     t->pending = false;
     t->batch_pending = 0;
@@ -131,8 +146,12 @@ extern "C" int gc_tree_select(gc_tree* t, float c_puct, float fpu, int32_t* d_pa
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
-    k_tree_select<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent, d_child,
-                                                                            d_action);
+    if (t->vslab)
+        k_tree_select<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent,
+                                                                                      d_child, d_action, t->v);
+    else
+        k_tree_select<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent,
+                                                                                       d_child, d_action, t->v);
     HIPCHK(hipGetLastError());
     t->pending = true;
     return 0;
@@ -149,7 +168,12 @@ extern "C" int gc_tree_backup(gc_tree* t, const float* d_value, const uint8_t* d
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
     const TreePriors p{d_actions, d_priors, d_count, pri_cap};
-    k_tree_backup<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, d_value, d_done, d_reason, p);
+    if (t->vslab)
+        k_tree_backup<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, d_value, d_done, d_reason, p,
+                                                                                      t->v);
+    else
+        k_tree_backup<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, d_value, d_done, d_reason,
+                                                                                       p, t->v);
     HIPCHK(hipGetLastError());
     t->pending = false;
     return 0;
@@ -180,7 +204,12 @@ extern "C" int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_
     const size_t lds = (size_t)TREE_WAVES * ((t->d.nodes + 63) / 64) * sizeof(unsigned long long);
     k_tree_advance_mark<<<tree_grid(t), dim3(64 * TREE_WAVES), lds, e->stream>>>(t->d, d_move, d_kept, remap);
     HIPCHK(hipGetLastError());
-    k_tree_advance_compact<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, e->stream>>>(t->d, p, d_value, d_kept, remap);
+    if (t->vslab)
+        k_tree_advance_compact<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, e->stream>>>(t->d, p, d_value, d_kept,
+                                                                                            remap, t->v);
+    else
+        k_tree_advance_compact<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, e->stream>>>(t->d, p, d_value, d_kept,
+                                                                                             remap, t->v);
     HIPCHK(hipGetLastError());
     CloneArgs a;
     a.sslab = e->slab;
@@ -204,7 +233,8 @@ extern "C" int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_
 extern "C" int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int flags, uint16_t* d_actions,
                                    int32_t* d_visits, float* d_pi, uint16_t* d_pick, float* d_value) {
     if (!t) return fail("null tree");
-    if (flags & ~1) return fail("flags: bit 0 = greedy; every other bit 0");
+    if (flags & ~3) return fail("flags: bit 0 = greedy, bit 1 = proofs (a solver tree); every other bit 0");
+    if ((flags & 2) && !t->vslab) return fail("flags bit 1 (proofs) needs a solver tree: gc_tree_solver_enable first");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     SRV_QUIESCE(t->e);
@@ -218,7 +248,11 @@ extern "C" int gc_tree_root_policy(gc_tree* t, uint64_t seed, uint32_t draw, int
     a.pi = d_pi;
     a.pick = d_pick;
     a.value = d_value;
-    k_tree_root_policy<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, a);
+    a.proof = (flags >> 1) & 1;
+    if (t->vslab)
+        k_tree_root_policy<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, a, t->v);
+    else
+        k_tree_root_policy<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, a, t->v);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -234,6 +268,7 @@ extern "C" int gc_tree_pointers(gc_tree* t, void** out, int n) {
 
 extern "C" int gc_tree_batch_reserve(gc_tree* t, int max_leaves) {
     if (!t) return fail("null tree");
+    if (t->vslab) return fail(TREE_SOLVER_NO_BATCH);
     if (max_leaves < 1 || max_leaves > 64) return fail("max_leaves must be in [1, 64]");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
@@ -276,6 +311,7 @@ extern "C" int gc_tree_batch_reserve(gc_tree* t, int max_leaves) {
 extern "C" int gc_tree_select_batch(gc_tree* t, int leaves, float c_puct, float fpu, float vloss, int32_t* d_parent,
                                     int32_t* d_child, uint16_t* d_action) {
     if (!t) return fail("null tree");
+    if (t->vslab) return fail(TREE_SOLVER_NO_BATCH);
     if (!d_parent || !d_child || !d_action) return fail("null output array");
     if (!t->bslab) return fail("no batch scratch: gc_tree_batch_reserve first");
     if (leaves < 1 || leaves > t->b.K) return fail("leaves must be in [1, the reserved max_leaves]");
@@ -297,6 +333,7 @@ extern "C" int gc_tree_backup_batch(gc_tree* t, const float* d_value, const uint
                                     const uint16_t* d_actions, const float* d_priors, const int32_t* d_count,
                                     int pri_cap) {
     if (!t) return fail("null tree");
+    if (t->vslab) return fail(TREE_SOLVER_NO_BATCH);
     if (!d_value || !d_done || !d_reason) return fail("null value / done / reason array");
     if (!d_actions || !d_priors || !d_count) return fail("null priors block");
     if (pri_cap < 1) return fail("pri_cap must be >= 1");
@@ -319,6 +356,61 @@ extern "C" int gc_tree_batch_pointers(gc_tree* t, void** out, int n) {
     const TreeBatchDev& b = t->b;
     void* p[GC_TREE_BATCH_ARRAYS] = {b.inflight, b.path, b.depth, b.leaf, b.kind, b.collisions};
     for (int k = 0; k < n && k < GC_TREE_BATCH_ARRAYS; k++) out[k] = p[k];
+    return 0;
+}
+
+extern "C" int gc_tree_solver_enable(gc_tree* t) {
+    if (!t) return fail("null tree");
+    if (t->vslab) return 0;
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
+    if (t->bslab) return fail("a batch scratch is reserved: the batch calls are not defined for a solver tree yet");
+    gc_env* e = t->e;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    const TreeDev& d = t->d;
+    size_t sz[GC_TREE_SOLVER_ARRAYS], off[GC_TREE_SOLVER_ARRAYS], total = 0;
+    tree_solver_sizes((size_t)d.games, (size_t)d.nodes, (size_t)d.cap, sz);
+    for (int k = 0; k < GC_TREE_SOLVER_ARRAYS; k++) {
+        off[k] = total;
+        total += (sz[k] + 255) & ~(size_t)255;
+    }
+    uint8_t* slab = nullptr;
+    if (dalloc(&slab, total)) return -1;
+    hipError_t rc = hipMemsetAsync(slab, 0, total, e->stream);
+    if (rc != hipSuccess) {
+        (void)hipFree(slab);
+        return fail(std::string("hipMemsetAsync: ") + hipGetErrorString(rc));
+    }
+    t->vslab = slab;
+    t->bytes += total;
+    TreeSolverDev& v = t->v;
+    v.edge_proven = slab + off[0];
+    v.edge_plies = (uint16_t*)(slab + off[1]);
+    v.node_proven = slab + off[2];
+    v.node_plies = (uint16_t*)(slab + off[3]);
+    v.complete = slab + off[4];
+    return 0;
+}
+
+extern "C" int gc_tree_solver_pointers(gc_tree* t, void** out, int n) {
+    if (!t || !out) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1");
+    if (!t->vslab) return fail("no solver: gc_tree_solver_enable first");
+    const TreeSolverDev& v = t->v;
+    void* p[GC_TREE_SOLVER_ARRAYS] = {v.edge_proven, v.edge_plies, v.node_proven, v.node_plies, v.complete};
+    for (int k = 0; k < n && k < GC_TREE_SOLVER_ARRAYS; k++) out[k] = p[k];
+    return 0;
+}
+
+extern "C" int gc_tree_root_proof(gc_tree* t, uint8_t* d_status, uint16_t* d_plies, uint16_t* d_move) {
+    if (!t) return fail("null tree");
+    if (!t->vslab) return fail("no solver: gc_tree_solver_enable first");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    k_tree_root_proof<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->v, d_status, d_plies, d_move);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

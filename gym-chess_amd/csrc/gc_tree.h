@@ -3,7 +3,10 @@
 // (k_tree_backup), the same for several leaves per game per call with a virtual loss
 // (k_tree_select_batch / k_tree_backup_batch), the root's visit distribution with a move
 // (k_tree_root_policy), and the played move's subtree kept across moves (k_tree_advance_mark /
-// k_tree_advance_compact, at the end) (gc_tree_*, include/gymchess.h).
+// k_tree_advance_compact, at the end) (gc_tree_*, include/gymchess.h).  The solver
+// (gc_tree_solver_enable: forced wins, draws and losses proven during the search) is the <true>
+// instantiation of k_tree_reset / select / backup / root_policy / advance_compact, plus
+// tree_propagate and k_tree_root_proof; the <false> instantiations never name its arrays.
 //
 // Geometry: G games, `nodes` nodes per game, `cap` child slots per node (1..256).  Node k of game
 // g is board g * nodes + k of the tree env; node 0 is the root.  Edge statistics live with the
@@ -60,6 +63,22 @@ struct TreePriors {
     int pri_cap;
 };
 
+// The solver's arrays (gc_tree_solver_enable; the header has the rules): proofs of forced wins,
+// draws and losses.  Status codes are seen from the side to move at the node / the side choosing
+// among the node's edges.  Every kernel that reads them is the <true> instantiation of a template
+// whose <false> one never names them, so a tree without the solver runs the code it always ran.
+#define TREE_UNKNOWN 0
+#define TREE_WIN 1
+#define TREE_DRAW 2
+#define TREE_LOSS 3
+struct TreeSolverDev {
+    uint8_t* edge_proven;  // [G][nodes][cap]
+    uint16_t* edge_plies;  // [G][nodes][cap]
+    uint8_t* node_proven;  // [G][nodes]
+    uint16_t* node_plies;  // [G][nodes]
+    uint8_t* complete;     // [G][nodes]
+};
+
 using TreeReduceI = hipcub::WarpReduce<int, 64>;
 using TreeReduceD = hipcub::WarpReduce<double, 64>;
 using TreeReduceU64 = hipcub::WarpReduce<unsigned long long, 64>;
@@ -100,10 +119,39 @@ __device__ __forceinline__ void tree_init_node(const TreeDev& T, int g, int node
     if (lane == 0) T.n_children[nb] = m;
 }
 
+// complete iff the list holds every legal move: the row's count fits both the block and the
+// tree's cap; a terminal node (!listed, the row unread) counts as complete.  (Called before
+// tree_init_node's stores, so that the count's load is one with its own.)
+__device__ __forceinline__ bool tree_row_complete(const TreeDev& T, int g, const TreePriors& P, bool listed) {
+    if (!listed) return true;
+    const int c = P.count[g];
+    return c >= 0 && c <= P.pri_cap && c <= T.cap;
+}
+
+// the solver's part of a new node: no edge proven; `status`: TREE_UNKNOWN, or a terminal node's
+// verdict, plies 0
+__device__ __forceinline__ void tree_solver_init_node(const TreeDev& T, const TreeSolverDev& V, int g, int node,
+                                                      bool complete, int status, int lane) {
+    const size_t nb = (size_t)g * T.nodes + node, o = nb * T.cap;
+    for (int s = lane; s < T.cap; s += 64) {
+        V.edge_proven[o + s] = TREE_UNKNOWN;
+        V.edge_plies[o + s] = 0;
+    }
+    if (lane == 0) {
+        V.complete[nb] = complete ? 1 : 0;
+        V.node_proven[nb] = (uint8_t)status;
+        V.node_plies[nb] = 0;
+    }
+}
+
 // game g a single root with the child list of row g of P
-__device__ __forceinline__ void tree_reset_game(const TreeDev& T, int g, const TreePriors& P, const float* value,
-                                                int lane) {
+template <bool SOLVER>
+__device__ __forceinline__ void tree_reset_game(const TreeDev& T, const TreeSolverDev& V, int g, const TreePriors& P,
+                                                const float* value, int lane) {
+    bool complete = false;
+    if constexpr (SOLVER) complete = tree_row_complete(T, g, P, true);
     tree_init_node(T, g, 0, P, true, lane);
+    if constexpr (SOLVER) tree_solver_init_node(T, V, g, 0, complete, TREE_UNKNOWN, lane);
     if (lane == 0) {
         const size_t nb = (size_t)g * T.nodes;
         T.parent[nb] = -1;
@@ -119,20 +167,66 @@ __device__ __forceinline__ void tree_reset_game(const TreeDev& T, int g, const T
 }
 
 // every game a single root with the child list of row g of P
+template <bool SOLVER>
 __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_reset(const TreeDev T, const TreePriors P,
-                                                                 const float* __restrict__ value) {
+                                                                 const float* __restrict__ value,
+                                                                 const TreeSolverDev V) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
-    tree_reset_game(T, g, P, value, lane);
+    tree_reset_game<SOLVER>(T, V, g, P, value, lane);
+}
+
+// the proof's slot among the first nc edges of the row at o: the edge of status `want` with the
+// fewest plies (TREE_WIN) or the most (TREE_LOSS), ties to the lowest slot; -1 without such an edge
+__device__ __forceinline__ int tree_proof_slot(const TreeSolverDev& V, size_t o, int nc, int want, int lane) {
+    unsigned long long key = 0;  // plies (a WIN's: 0xFFFF - plies) << 32 | ~slot; 0 = no such edge
+    for (int s = lane; s < nc; s += 64) {
+        if ((int)V.edge_proven[o + s] != want) continue;
+        const u32 pl = V.edge_plies[o + s];
+        const unsigned long long mine =
+            ((unsigned long long)(want == TREE_WIN ? 0xFFFFu - pl : pl) << 32) | (0xFFFFFFFFu - (u32)s);
+        key = mine > key ? mine : key;
+    }
+    key = tree_wave_max(key);
+    return __builtin_amdgcn_readfirstlane(key ? (int)(0xFFFFFFFFu - (u32)key) : -1);
+}
+
+// the node rule over the first nc edges of the row at o, with edge j taken as (sj, pj) from the
+// caller's registers (the row's stored entry j is not read): status | plies << 8, wave-uniform
+__device__ __forceinline__ u32 tree_node_rule(const TreeSolverDev& V, size_t o, int nc, bool complete, int j, int sj,
+                                              int pj, int lane) {
+    int wmin = 0x10000, amax = 0;
+    bool unknown = false, draw = false;
+    for (int s = lane; s < nc; s += 64) {
+        const int st = s == j ? sj : (int)V.edge_proven[o + s];
+        const int pl = s == j ? pj : (int)V.edge_plies[o + s];
+        if (st == TREE_WIN) wmin = pl < wmin ? pl : wmin;
+        unknown |= st == TREE_UNKNOWN;
+        draw |= st == TREE_DRAW;
+        amax = pl > amax ? pl : amax;
+    }
+    TreeReduceI::TempStorage ts;
+    wmin = __builtin_amdgcn_readfirstlane(TreeReduceI(ts).Reduce(wmin, hipcub::Min()));
+    if (wmin < 0x10000) return TREE_WIN | (u32)wmin << 8;
+    if (!complete || __ballot(unknown)) return TREE_UNKNOWN;
+    if (__ballot(draw)) return TREE_DRAW;
+    amax = __builtin_amdgcn_readfirstlane(TreeReduceI(ts).Reduce(amax, hipcub::Max()));
+    return TREE_LOSS | (u32)amax << 8;
 }
 
 // PUCT descent of every game to one leaf (the header's contract has the rule and the three ways
 // it ends).  score_j = Q_j + c_puct * prior_j * sqrt(n_k) / (1 + visits_j) in fp32, in exactly
 // this order of operations; the largest score wins, ties to the lowest slot.
+// SOLVER: the node's edge_proven row joins the loads of the level's one round trip.  A proven
+// edge scores with Q = +1 / 0 / -1, LOSS edges leave the argmax unless all are LOSS, a node with
+// a WIN edge (only ever the root) takes the proof's slot, and a descent that chooses a proven edge
+// ends at its child (the header's "Select on a solver tree").
+template <bool SOLVER>
 __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T, float c_puct, float fpu,
                                                                   int32_t* __restrict__ out_parent,
                                                                   int32_t* __restrict__ out_child,
-                                                                  uint16_t* __restrict__ out_action) {
+                                                                  uint16_t* __restrict__ out_action,
+                                                                  const TreeSolverDev V) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
     const float ninf = -__builtin_inff();
@@ -148,6 +242,10 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T
         const size_t o = (gb + k) * T.cap;
         // chunk 0 of the node's rows together with its child count: one round trip
         const bool in0 = lane < T.cap;
+        // (SOLVER: issued first and without a branch -- slot 0 exists in every row -- so that it
+        // is in flight with the others; a lane at or past nc holds a value nothing below reads)
+        int ep0 = TREE_UNKNOWN;
+        if constexpr (SOLVER) ep0 = (int)V.edge_proven[o + (in0 ? lane : 0)];
         int nc = __builtin_amdgcn_readfirstlane(T.n_children[gb + k]);
         nc = nc < T.cap ? nc : T.cap;
         int ev0 = in0 ? T.edge_visits[o + lane] : 0;
@@ -165,48 +263,75 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T
         }
         total = tree_wave_sum(total);
         const float sq = sqrtf((float)(1 + total));
-        auto score = [&](int ev, float val, float pr) {
-            const float q = ev ? val / (float)ev : fpu;
+        auto score = [&](int ev, float val, float pr, int ep) {
+            float q = ev ? val / (float)ev : fpu;
+            if constexpr (SOLVER) q = ep == TREE_UNKNOWN ? q : ep == TREE_WIN ? 1.0f : ep == TREE_DRAW ? 0.0f : -1.0f;
             return q + c_puct * pr * sq / (float)(1 + ev);
         };
+        // SOLVER: the edges left out of the argmax (LOSS, unless every edge is), and a WIN edge
+        bool drop_loss = false, won = false;
+        if constexpr (SOLVER) {
+            int n_loss = __popcll(__ballot(lane < nc && ep0 == TREE_LOSS));
+            won = __ballot(lane < nc && ep0 == TREE_WIN) != 0;
+            for (int c = 1; c < chunks; c++) {
+                const int s = c * 64 + lane;
+                const int ep = s < nc ? (int)V.edge_proven[o + s] : TREE_UNKNOWN;
+                n_loss += __popcll(__ballot(ep == TREE_LOSS));
+                won |= __ballot(ep == TREE_WIN) != 0;
+            }
+            drop_loss = n_loss < nc;
+        }
         float best = ninf;
         int j = -1;
-        {
-            const bool on = lane < nc;
-            const float sc = on ? score(ev0, val0, pr0) : ninf;
-            const float mx = pol_wave_max(sc);
-            const unsigned long long hit = __ballot(on && sc == mx);
-            if (hit) {
-                best = mx;
-                j = (int)__builtin_ctzll(hit);
+        if (SOLVER && won) {
+            j = tree_proof_slot(V, o, nc, TREE_WIN, lane);
+        } else {
+            {
+                const bool on = lane < nc && !(SOLVER && drop_loss && ep0 == TREE_LOSS);
+                const float sc = on ? score(ev0, val0, pr0, ep0) : ninf;
+                const float mx = pol_wave_max(sc);
+                const unsigned long long hit = __ballot(on && sc == mx);
+                if (hit) {
+                    best = mx;
+                    j = (int)__builtin_ctzll(hit);
+                }
             }
-        }
-        for (int c = 1; c < chunks; c++) {
-            const int s = c * 64 + lane;
-            const bool on = s < nc;
-            const float sc = on ? score(T.edge_visits[o + s], T.edge_value[o + s], T.prior[o + s]) : ninf;
-            const float mx = pol_wave_max(sc);
-            const unsigned long long hit = __ballot(on && sc == mx);
-            if (hit && (j < 0 || mx > best)) {  // an earlier chunk keeps a tie
-                best = mx;
-                j = c * 64 + (int)__builtin_ctzll(hit);
+            for (int c = 1; c < chunks; c++) {
+                const int s = c * 64 + lane;
+                int ep = TREE_UNKNOWN;
+                if constexpr (SOLVER) ep = s < nc ? (int)V.edge_proven[o + s] : TREE_UNKNOWN;
+                const bool on = s < nc && !(SOLVER && drop_loss && ep == TREE_LOSS);
+                const float sc = on ? score(T.edge_visits[o + s], T.edge_value[o + s], T.prior[o + s], ep) : ninf;
+                const float mx = pol_wave_max(sc);
+                const unsigned long long hit = __ballot(on && sc == mx);
+                if (hit && (j < 0 || mx > best)) {  // an earlier chunk keeps a tie
+                    best = mx;
+                    j = c * 64 + (int)__builtin_ctzll(hit);
+                }
             }
         }
         if (j < 0) j = 0;  // (only with NaN scores: some slot, in bounds)
-        int ch;
+        int ch, epj = TREE_UNKNOWN;
         u32 ac;
         if (j < 64) {
             ch = __builtin_amdgcn_readfirstlane(__shfl(ch0, j, 64));
             ac = __builtin_amdgcn_readfirstlane(__shfl(ac0, j, 64));
+            if constexpr (SOLVER) epj = __builtin_amdgcn_readfirstlane(__shfl(ep0, j, 64));
         } else {
             ch = __builtin_amdgcn_readfirstlane(T.child[o + j]);
             ac = __builtin_amdgcn_readfirstlane((u32)T.action[o + j]);
+            if constexpr (SOLVER) epj = __builtin_amdgcn_readfirstlane((int)V.edge_proven[o + j]);
         }
         if (lane == 0) {
             path[2 * D] = k;
             path[2 * D + 1] = j;
         }
         D++;
+        if (SOLVER && epj != TREE_UNKNOWN && ch >= 0 && ch < T.nodes) {  // a proven edge: the path ends at its child
+            leaf = ch;
+            k = -1;
+            break;
+        }
         if (ch >= 0 && ch < T.nodes) {  // descend
             k = ch;
             continue;
@@ -237,11 +362,55 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T
     }
 }
 
+// A new terminal leaf's verdict carried up the pending path (the header's "Propagation"), by the
+// game's own wave.  Ordering: nothing a lane stores here is loaded by another lane of this launch.
+//  * the status of the node below (first the leaf's, from done / reason; then node k's, just
+//    recomputed) travels from level to level in wave-uniform registers, never through node_proven;
+//  * edge (k, j) is stored by the lane that owns slot j and enters the node rule from registers
+//    (tree_node_rule takes it as an argument and skips the stored entry);
+//  * every other entry of k's rows, n_children[k], complete[k] and the stored verdict of k that
+//    step 5 compares with were written by EARLIER launches: a path holds distinct nodes, none of
+//    them the leaf, so this launch has stored nothing of k before level d is reached;
+//  * the path itself was written by the select launch.
+// So the stream's kernel boundary is the only ordering needed: no fence, no atomics.
+__device__ __forceinline__ void tree_propagate(const TreeDev& T, const TreeSolverDev& V, size_t gb,
+                                               const int32_t* path, int D, int status, int lane) {
+    int cs = status, cp = 0;  // the node below: its status and plies
+    for (int d = D - 1; d >= 0 && cs != TREE_UNKNOWN; d--) {
+        const int k = __builtin_amdgcn_readfirstlane(path[2 * d]), j = __builtin_amdgcn_readfirstlane(path[2 * d + 1]);
+        if ((unsigned)k >= (unsigned)T.nodes || (unsigned)j >= (unsigned)T.cap) break;
+        const size_t o = (gb + k) * T.cap;
+        int nc = __builtin_amdgcn_readfirstlane(T.n_children[gb + k]);
+        nc = nc < T.cap ? nc : T.cap;
+        const bool complete = __builtin_amdgcn_readfirstlane((int)V.complete[gb + k]) != 0;
+        const int os = __builtin_amdgcn_readfirstlane((int)V.node_proven[gb + k]);
+        const int op = __builtin_amdgcn_readfirstlane((int)V.node_plies[gb + k]);
+        const int es = cs == TREE_WIN ? TREE_LOSS : cs == TREE_LOSS ? TREE_WIN : cs;
+        const int ep = cp + 1 < 65535 ? cp + 1 : 65535;
+        if (lane == (j & 63)) {
+            V.edge_proven[o + j] = (uint8_t)es;
+            V.edge_plies[o + j] = (uint16_t)ep;
+        }
+        const u32 r = tree_node_rule(V, o, nc, complete, j, es, ep, lane);
+        const int ns = (int)(r & 0xFFu), np = (int)(r >> 8);
+        if (ns == os && np == op) break;
+        if (lane == 0) {
+            V.node_proven[gb + k] = (uint8_t)ns;
+            V.node_plies[gb + k] = (uint16_t)np;
+        }
+        cs = ns;
+        cp = np;
+    }
+}
+
 // the pending leaf created (a new one) and its value added along the pending path
+// SOLVER: a new node gets its solver rows, a new terminal one is propagated, and a proven leaf is
+// worth its verdict
+template <bool SOLVER>
 __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup(const TreeDev T, const float* __restrict__ value,
                                                                   const uint8_t* __restrict__ done,
                                                                   const uint8_t* __restrict__ reason,
-                                                                  const TreePriors P) {
+                                                                  const TreePriors P, const TreeSolverDev V) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
     const size_t gb = (size_t)g * T.nodes;
@@ -252,6 +421,8 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup(const TreeDev T
     if (T.leaf_new[g]) {
         const bool fin = done[g] != 0;
         v = fin ? (reason[g] == 1 ? -1.0f : 0.0f) : value[g];  // reason 1: the side to move at L is mated
+        bool complete = false;
+        if constexpr (SOLVER) complete = tree_row_complete(T, g, P, !fin);
         tree_init_node(T, g, L, P, !fin, lane);
         if (lane == 0 && D > 0) {
             const int pk = path[2 * (D - 1)], pj = path[2 * (D - 1) + 1];
@@ -261,8 +432,17 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_backup(const TreeDev T
             T.terminal[gb + L] = fin ? 1 : 0;
             if ((unsigned)pk < (unsigned)T.nodes && (unsigned)pj < (unsigned)T.cap) T.child[(gb + pk) * T.cap + pj] = L;
         }
+        if constexpr (SOLVER) {
+            const int status = fin ? (reason[g] == 1 ? TREE_LOSS : TREE_DRAW) : TREE_UNKNOWN;
+            tree_solver_init_node(T, V, g, L, complete, status, lane);
+            if (fin) tree_propagate(T, V, gb, path, D, status, lane);
+        }
     } else {
         v = T.leaf_value[gb + L];
+        if constexpr (SOLVER) {
+            const int st = V.node_proven[gb + L];
+            v = st == TREE_UNKNOWN ? v : st == TREE_WIN ? 1.0f : st == TREE_DRAW ? 0.0f : -1.0f;
+        }
     }
     // one lane per path entry: the entries name distinct nodes, so the stores are independent
     for (int d = lane; d < D; d += 64) {
@@ -492,10 +672,17 @@ struct TreeRootArgs {
     float* pi;          // [G][cap], may be NULL
     uint16_t* pick;     // [G], may be NULL
     float* value;       // [G], may be NULL
+    int proof;          // flag bit 1 (a solver tree only): the pick respects the root's proofs
 };
 
 // the root's visit counts, their distribution, the root value and a move per game
-__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const TreeDev T, const TreeRootArgs A) {
+// SOLVER with A.proof: only the pick changes (the header's "Root policy, flag bit 1").  `fixed`
+// is the slot a proof decides alone (a WIN edge; all edges LOSS; candidates without visits);
+// otherwise the greedy / sampled rule below runs over the candidates' visits (a LOSS edge counts
+// as 0 visits and is never chosen), which for a tree without proofs are all the visits.
+template <bool SOLVER>
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const TreeDev T, const TreeRootArgs A,
+                                                                       const TreeSolverDev V) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
     const size_t o = (size_t)g * T.nodes * T.cap, w = (size_t)g * T.cap;
@@ -514,12 +701,40 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const Tree
     total = tree_wave_sum(total);
     vsum = tree_wave_sum(vsum);
     if (lane == 0 && A.value) A.value[g] = total > 0 ? (float)(vsum / (double)total) : 0.f;
+    const bool proof = SOLVER && A.proof;
+    int ptotal = total;  // the visits the pick is drawn from
+    bool fixed = false;
+    u32 pick = TREE_NO_ACTION;
+    if constexpr (SOLVER) {
+        if (proof) {
+            int cv = 0, first = TREE_MAX_CAP;  // the candidates' visits, the lowest candidate slot
+            bool won = false;
+            for (int c = 0; c < chunks; c++) {
+                const int s = c * 64 + lane;
+                const int ep = s < nc ? (int)V.edge_proven[o + s] : TREE_LOSS;
+                const unsigned long long cand = __ballot(s < nc && ep != TREE_LOSS);
+                won |= __ballot(s < nc && ep == TREE_WIN) != 0;
+                if (cand && first == TREE_MAX_CAP) first = c * 64 + (int)__builtin_ctzll(cand);
+                cv += s < nc && ep != TREE_LOSS ? T.edge_visits[o + s] : 0;
+            }
+            ptotal = tree_wave_sum(cv);
+            int slot = -1;
+            if (won) {
+                slot = tree_proof_slot(V, o, nc, TREE_WIN, lane);
+            } else if (first == TREE_MAX_CAP) {
+                slot = tree_proof_slot(V, o, nc, TREE_LOSS, lane);
+            } else if (ptotal == 0) {
+                slot = total > 0 ? first : -1;
+            }
+            fixed = won || first == TREE_MAX_CAP || ptotal == 0;
+            if (slot >= 0 && slot < nc) pick = T.action[o + slot];
+        }
+    }
     // greedy: the most visited slot, ties to the lowest; sampled: the first slot whose inclusive
     // visit prefix exceeds r = ((x0 >> 8) * total) >> 24, the sampler's Philox word (gc_policy.h)
-    const u64 r = total > 0 ? (((u64)(philox_x0(A.seed, (u32)g, A.draw) >> 8) * (u64)total) >> 24) : 0;
+    const u64 r = ptotal > 0 ? (((u64)(philox_x0(A.seed, (u32)g, A.draw) >> 8) * (u64)ptotal) >> 24) : 0;
     unsigned long long key = 0;  // visits << 32 | ~slot
     u32 carry = 0;
-    u32 pick = TREE_NO_ACTION;
     for (int c = 0; c < chunks; c++) {
         const int s = c * 64 + lane;
         const bool in = s < T.cap, on = s < nc;
@@ -530,22 +745,45 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_policy(const Tree
             if (A.visits) A.visits[w + s] = ev;
             if (A.pi) A.pi[w + s] = total > 0 ? (float)ev / (float)total : 0.f;
         }
+        bool can = on;  // a candidate of the pick
+        if constexpr (SOLVER) can = on && !(proof && V.edge_proven[o + s] == TREE_LOSS);
+        const int pv = can ? ev : 0;
         if (A.greedy) {
-            const unsigned long long mine = on ? ((unsigned long long)(u32)ev << 32) | (0xFFFFFFFFu - (u32)s) : 0ull;
+            const unsigned long long mine = can ? ((unsigned long long)(u32)pv << 32) | (0xFFFFFFFFu - (u32)s) : 0ull;
             key = mine > key ? mine : key;
         } else {
-            const u32 incl = carry + pol_wave_scan((u32)ev);
-            const unsigned long long hit = __ballot(on && (u64)incl > r && (u64)(incl - (u32)ev) <= r);
-            if (hit && pick == TREE_NO_ACTION && total > 0) pick = __shfl(ac, (int)__builtin_ctzll(hit), 64);
+            const u32 incl = carry + pol_wave_scan((u32)pv);
+            const unsigned long long hit = __ballot(can && (u64)incl > r && (u64)(incl - (u32)pv) <= r);
+            if (hit && pick == TREE_NO_ACTION && ptotal > 0 && !fixed) pick = __shfl(ac, (int)__builtin_ctzll(hit), 64);
             carry = __shfl(incl, 63, 64);
         }
     }
-    if (A.greedy && total > 0) {
+    if (A.greedy && ptotal > 0 && !fixed) {
         key = tree_wave_max(key);
         const int s = (int)(0xFFFFFFFFu - (u32)key);
         if (s >= 0 && s < nc) pick = T.action[o + s];
     }
     if (lane == 0 && A.pick) A.pick[g] = (uint16_t)pick;
+}
+
+// the root's status, its plies and the proof's move per game (the header's gc_tree_root_proof)
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_proof(const TreeDev T, const TreeSolverDev V,
+                                                                      uint8_t* __restrict__ out_status,
+                                                                      uint16_t* __restrict__ out_plies,
+                                                                      uint16_t* __restrict__ out_move) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const size_t nb = (size_t)g * T.nodes, o = nb * T.cap;
+    int nc = __builtin_amdgcn_readfirstlane(T.n_children[nb]);
+    nc = nc < T.cap ? nc : T.cap;
+    const int st = __builtin_amdgcn_readfirstlane((int)V.node_proven[nb]);
+    int slot = -1;
+    if (st == TREE_WIN || st == TREE_LOSS) slot = tree_proof_slot(V, o, nc, st, lane);
+    if (lane == 0) {
+        if (out_status) out_status[g] = (uint8_t)st;
+        if (out_plies) out_plies[g] = V.node_plies[nb];
+        if (out_move) out_move[g] = slot >= 0 ? T.action[o + slot] : (uint16_t)TREE_NO_ACTION;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -628,15 +866,18 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_mark(const Tre
 }
 
 // a kept game's rows moved to their new indices with the links renumbered; a fresh game reset
+// SOLVER: the solver's rows and scalars move with their nodes, the same lanes owning them
+template <bool SOLVER>
 __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const TreeDev T, const TreePriors P,
                                                                            const float* __restrict__ value,
                                                                            const int32_t* __restrict__ kept,
-                                                                           const int32_t* __restrict__ remap) {
+                                                                           const int32_t* __restrict__ remap,
+                                                                           const TreeSolverDev V) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
     const int m = __builtin_amdgcn_readfirstlane(kept[g]);
     if (m <= 0) {
-        tree_reset_game(T, g, P, value, lane);
+        tree_reset_game<SOLVER>(T, V, g, P, value, lane);
         return;
     }
     const size_t gb = (size_t)g * T.nodes;
@@ -664,6 +905,8 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const 
                 uint16_t ac[TREE_ADV_AHEAD];
                 float pr[TREE_ADV_AHEAD], va[TREE_ADV_AHEAD];
                 int ch[TREE_ADV_AHEAD], ev[TREE_ADV_AHEAD];
+                uint8_t ep[TREE_ADV_AHEAD];
+                uint16_t pl[TREE_ADV_AHEAD];
 #pragma unroll
                 for (int u = 0; u < TREE_ADV_AHEAD; u++) {
                     if (from[u] < 0) continue;
@@ -673,6 +916,10 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const 
                     ch[u] = T.child[o];
                     ev[u] = T.edge_visits[o];
                     va[u] = T.edge_value[o];
+                    if constexpr (SOLVER) {
+                        ep[u] = V.edge_proven[o];
+                        pl[u] = V.edge_plies[o];
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < TREE_ADV_AHEAD; u++)
@@ -686,12 +933,17 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const 
                     T.child[o] = ch[u];
                     T.edge_visits[o] = ev[u];
                     T.edge_value[o] = va[u];
+                    if constexpr (SOLVER) {
+                        V.edge_proven[o] = ep[u];
+                        V.edge_plies[o] = pl[u];
+                    }
                 }
             }
             if (lane == 0) {
                 int nch[TREE_ADV_AHEAD], pa[TREE_ADV_AHEAD], ps[TREE_ADV_AHEAD];
                 float lv[TREE_ADV_AHEAD];
-                uint8_t te[TREE_ADV_AHEAD];
+                uint8_t te[TREE_ADV_AHEAD], np[TREE_ADV_AHEAD], co[TREE_ADV_AHEAD];
+                uint16_t npl[TREE_ADV_AHEAD];
 #pragma unroll
                 for (int u = 0; u < TREE_ADV_AHEAD; u++) {
                     if (from[u] < 0) continue;
@@ -701,6 +953,11 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const 
                     ps[u] = T.parent_slot[o];
                     lv[u] = T.leaf_value[o];
                     te[u] = T.terminal[o];
+                    if constexpr (SOLVER) {
+                        np[u] = V.node_proven[o];
+                        npl[u] = V.node_plies[o];
+                        co[u] = V.complete[o];
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < TREE_ADV_AHEAD; u++) {
@@ -718,6 +975,11 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_advance_compact(const 
                     T.parent_slot[o] = ps[u];
                     T.leaf_value[o] = lv[u];
                     T.terminal[o] = te[u];
+                    if constexpr (SOLVER) {
+                        V.node_proven[o] = np[u];
+                        V.node_plies[o] = npl[u];
+                        V.complete[o] = co[u];
+                    }
                 }
             }
         }

@@ -104,6 +104,9 @@ SIGNATURES = {
     "gc_tree_select_batch": (_I, [_P, _I, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P, _P]),
     "gc_tree_backup_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _I]),
     "gc_tree_batch_pointers": (_I, [_P, _P, _I]),
+    "gc_tree_solver_enable": (_I, [_P]),
+    "gc_tree_solver_pointers": (_I, [_P, _P, _I]),
+    "gc_tree_root_proof": (_I, [_P, _P, _P, _P]),
     "gc_tree_device_bytes": (_U64, [_P]),
     "gc_replay_create": (_I, [_P, _I, _I, _I, ctypes.c_int64, _P]),
     "gc_replay_destroy": (_I, [_P]),

@@ -621,11 +621,12 @@ class BatchedChessEnv:
         return int(v.value)
 
     # ------------------------------------------------------------------ the search tree
-    def search_tree(self, games, nodes, cap=64):
+    def search_tree(self, games, nodes, cap=64, solver=False):
         """A batched PUCT tree over this (tree) env's boards (gc_tree_*): `games` trees of up to
-        `nodes` nodes with `cap` child slots each; node k of game g is board g * nodes + k.  See
+        `nodes` nodes with `cap` child slots each; node k of game g is board g * nodes + k.
+        solver=True: the tree proves forced wins, draws and losses as it searches.  See
         SearchTree."""
-        t = SearchTree(self, games, nodes, cap=cap)
+        t = SearchTree(self, games, nodes, cap=cap, solver=solver)
         if not hasattr(self, "_trees"):
             self._trees = []
         self._trees.append(weakref.ref(t))
@@ -924,16 +925,28 @@ class SearchTree:
                                      ascending (value: device float32[G * leaves]; rows / pri:
                                      buffers of at least G * leaves rows)
 
-    ptr[...] are the device addresses of the tree's arrays (ARRAYS, and BATCH_ARRAYS once
-    reserved), fetch(*keys) host copies (no keys: ARRAYS)."""
+    The solver (search_tree(..., solver=True) or enable_solver(); gc_tree_solver_enable): terminal
+    verdicts are propagated up the path as proofs (status 0 unknown, 1 WIN, 2 DRAW, 3 LOSS for the
+    side to move, with the plies to the end); select scores proven edges exactly, avoids lost ones
+    and stops at a proven edge; one leaf per game per call (the batch calls refuse a solver tree):
+
+        proof = root_proof()         status uint8[G] / plies uint16[G] / move uint16[G] of every
+                                     root (device pointers, .fetch()); move 0xFFFF unless WIN / LOSS
+        root_policy(..., proof=True) the pick plays a proven win, and otherwise never a move that
+                                     is proven lost while another is not; the other outputs are unchanged
+
+    ptr[...] are the device addresses of the tree's arrays (ARRAYS, BATCH_ARRAYS once reserved and
+    SOLVER_ARRAYS once enabled), fetch(*keys) host copies (no keys: ARRAYS)."""
 
     ARRAYS = ("action", "prior", "child", "edge_visits", "edge_value", "n_children", "parent", "parent_slot",
               "leaf_value", "terminal", "n_nodes", "overflow", "depth", "leaf", "leaf_new", "path")
     BATCH_ARRAYS = ("inflight", "b_path", "b_depth", "b_leaf", "b_kind", "collisions")
+    SOLVER_ARRAYS = ("edge_proven", "edge_plies", "node_proven", "node_plies", "complete")
     _DTYPES = {"action": np.uint16, "prior": np.float32, "edge_value": np.float32, "leaf_value": np.float32,
-               "terminal": np.uint8, "inflight": np.uint8}
+               "terminal": np.uint8, "inflight": np.uint8, "edge_proven": np.uint8, "edge_plies": np.uint16,
+               "node_proven": np.uint8, "node_plies": np.uint16, "complete": np.uint8}
 
-    def __init__(self, env, games, nodes, cap=64):
+    def __init__(self, env, games, nodes, cap=64, solver=False):
         self.env, self.games, self.nodes, self.cap = env, int(games), int(nodes), int(cap)
         self._L = env._L
         self._h = None
@@ -954,9 +967,39 @@ class SearchTree:
         self.max_leaves = 0  # reserve_batch()'s size
         self._bsel = None  # select_batch()'s buffers, games * max_leaves rows
         self._batch = 0  # leaves per game of the pending batch
+        self.solver = False
+        self._proof = None  # root_proof()'s buffers, made by enable_solver()
+        if solver:
+            self.enable_solver()
+
+    def enable_solver(self):
+        """turns the solver on (gc_tree_solver_enable: once, and only while nothing is pending and
+        no batch scratch is reserved); its arrays join ptr[...] / fetch()"""
+        _lib.check(self._L.gc_tree_solver_enable(self._h))
+        addr = (ctypes.c_void_p * len(self.SOLVER_ARRAYS))()
+        _lib.check(self._L.gc_tree_solver_pointers(self._h, addr, len(self.SOLVER_ARRAYS)))
+        self.ptr.update({k: addr[i] for i, k in enumerate(self.SOLVER_ARRAYS)})
+        if self._proof is None:
+            G = self.games
+            self._proof = _DeviceArrays(self.env, {"status": (np.uint8, (G,)), "plies": (np.uint16, (G,)),
+                                                   "move": (np.uint16, (G,))})
+        self.solver = True
+
+    def root_proof(self):
+        """the roots' proofs (gc_tree_root_proof): status uint8[G] (0 unknown, 1 WIN, 2 DRAW, 3
+        LOSS for the side to move), plies uint16[G] and move uint16[G] (the fastest win / the
+        longest loss, 0xFFFF otherwise); returns the tree's buffers (device pointers as attributes,
+        .fetch())"""
+        if self._proof is None:
+            raise ValueError("root_proof: a solver tree (search_tree(..., solver=True) or enable_solver())")
+        r = self._proof.ptr
+        _lib.check(self._L.gc_tree_root_proof(self._h, r["status"], r["plies"], r["move"]))
+        return self._proof
 
     def _shape(self, k):
         G, N, C_ = self.games, self.nodes, self.cap
+        if k in self.SOLVER_ARRAYS:
+            return (G, N, C_) if k.startswith("edge_") else (G, N)
         if k in self.BATCH_ARRAYS:
             K = self.max_leaves
             return {"inflight": (G, N, C_), "b_path": (G, K, N, 2), "collisions": (G,)}.get(k, (G, K))
@@ -1048,14 +1091,16 @@ class SearchTree:
         _lib.check(self._L.gc_tree_backup_batch(self._h, int(value), rows.ptr["done"], rows.ptr["reason"], a, p, c, pc))
         self._batch = 0
 
-    def root_policy(self, greedy=False, seed=None, draw=0):
+    def root_policy(self, greedy=False, seed=None, draw=0, proof=False):
         """the roots' actions uint16[G][cap], visits int32[G][cap], pi float32[G][cap], value
         float32[G] and a move pick uint16[G] (greedy: the most visited; else sampled in
         proportion to the visits from the Philox stream (seed, game, draw); seed None = the
-        env's); returns the tree's buffers (device pointers as attributes, .fetch())"""
+        env's; proof (a solver tree): a proven win is played, a move proven lost is left out
+        while another is not); returns the tree's buffers (device pointers as attributes, .fetch())"""
         r = self._root.ptr
         _lib.check(self._L.gc_tree_root_policy(self._h, ctypes.c_uint64(self.env.seed if seed is None else int(seed)),
-                                               int(draw) & 0xFFFFFFFF, int(bool(greedy)), r["actions"], r["visits"],
+                                               int(draw) & 0xFFFFFFFF, int(bool(greedy)) | 2 * int(bool(proof)),
+                                               r["actions"], r["visits"],
                                                r["pi"], r["pick"], r["value"]))
         return self._root
 
@@ -1116,6 +1161,9 @@ class SearchTree:
             if self._moves is not None:
                 self._moves.close()
                 self._moves = None
+            if self._proof is not None:
+                self._proof.close()
+                self._proof = None
             self.ptr = {}
 
     def __del__(self):

@@ -479,9 +479,76 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * a batch is pending, gc_tree_backup_batch fails without one.  gc_tree_select_batch also fails,
  * with nothing launched, on leaves outside 1..max_leaves or nothing reserved, a vloss that is not
  * finite or < 0, gc_tree_select's c_puct / fpu rules and a NULL output; gc_tree_backup_batch on
- * what gc_tree_backup refuses; gc_tree_batch_pointers with nothing reserved. */
+ * what gc_tree_backup refuses; gc_tree_batch_pointers with nothing reserved.
+ * The solver (MCTS-Solver, "certainty propagation"): an opt-in mode of a handle that proves forced
+ * wins, draws and losses during the search.  Every node owns its board and its own 3-fold window
+ * and there are no transpositions, so a terminal verdict is exact for the path that reached it and
+ * a proof never becomes invalid.  A tree that never calls gc_tree_solver_enable behaves exactly as
+ * described above.  Status codes, from the view of the side to move at the node / the side choosing
+ * among the node's edges: 0 unknown, 1 WIN, 2 DRAW, 3 LOSS.
+ * gc_tree_solver_enable allocates the arrays below (one allocation, zero-filled on e's stream,
+ * counted by gc_tree_device_bytes from then on); a second call does nothing.  It fails while a
+ * selection is pending and when a batch scratch is reserved.  Enabling on a tree that already has
+ * nodes is sound: those nodes are unknown and incomplete, so they can only ever be proven WIN.
+ * gc_tree_solver_pointers hands the arrays out in this order (GC_TREE_SOLVER_ARRAYS of them; the
+ * first min(n, GC_TREE_SOLVER_ARRAYS), n >= 1); it fails before the solver is enabled:
+ *    0 edge_proven u8  [games][nodes][cap]   status of playing slot j, for the side to move at
+ *                                            this node (with the parent, like every edge statistic)
+ *    1 edge_plies  u16 [games][nodes][cap]   plies to the end under the proof, 0 while unknown
+ *    2 node_proven u8  [games][nodes]
+ *    3 node_plies  u16 [games][nodes]
+ *    4 complete    u8  [games][nodes]        1 iff the child list holds ALL the node's legal moves:
+ *                                            the row it was made from had 0 <= count <= min(pri_cap,
+ *                                            cap); a terminal node counts as complete
+ * All rules are integer and deterministic.
+ * Node creation (reset, backup, a fresh game in advance): the node's edge_proven / edge_plies rows
+ * are zeroed and complete is set as above; a new TERMINAL node gets node_proven = d_reason == 1 ?
+ * LOSS : DRAW, plies 0; every other new node is unknown.  A childless node that is not terminal
+ * stays unknown for ever (the reference rules have no stalemate verdict; the network's value stands).
+ * Node rule, for a node with m = n_children > 0 edges: if any edge is WIN the node is WIN, its
+ * plies the minimum over its WIN edges; otherwise, if complete is set and no edge is unknown, it is
+ * DRAW with plies 0 if any edge is DRAW, else LOSS with plies the maximum over its edges; otherwise
+ * it is unknown (plies 0).
+ * Propagation, in gc_tree_backup, only when the pending leaf is new and terminal, after the leaf
+ * is created and before the value adds: for d = D - 1 down to 0, with (k, j) = path[d] and c the
+ * node below it (the leaf for d = D - 1): (1) if node_proven[c] is unknown, stop; (2)
+ * edge_proven[k][j] = c's status with WIN and LOSS swapped; (3) edge_plies[k][j] = min(65535,
+ * node_plies[c] + 1); (4) node k is recomputed by the node rule; (5) if its status and plies equal
+ * the stored ones, stop, otherwise they are stored and the loop goes on.
+ * gc_tree_select on a solver tree, at node k: a proven edge scores with Q_j = +1 / 0 / -1 (WIN /
+ * DRAW / LOSS) in place of edge_value / edge_visits, everything else in the score unchanged and in
+ * the same order of operations; edges proven LOSS are left out of the argmax unless every edge of
+ * the node is LOSS; at a node that is proven WIN (only the root can be entered in that state) the
+ * slot is the WIN edge with the fewest plies, ties to the lowest slot, and no scores are involved.
+ * (k, j) is appended to the path as always.  If edge_proven[k][j] != 0 the descent ends at
+ * child[k][j] (which exists: the proof came from it): leaf_new 0, outputs -1 / -1 / 0xFFFF, and the
+ * env calls skip the row exactly as they skip a terminal one; otherwise it goes on as above, cases
+ * (a), (b) and (c) unchanged.
+ * gc_tree_backup on a solver tree: v = +1 / 0 / -1 (WIN / DRAW / LOSS) from node_proven[L] when
+ * the leaf is proven, else leaf_value[L] (for terminal nodes the two coincide); the value adds are
+ * otherwise unchanged, one fp32 add per edge in the same order.
+ * gc_tree_advance on a solver tree: the five arrays move with their nodes, edge rows and node
+ * scalars arriving at the new index bit for bit; a kept root keeps its status; a fresh game is
+ * reset as above.
+ * gc_tree_root_proof (one launch; every output may be NULL): per game d_status[g] / d_plies[g] =
+ * the root's node_proven / node_plies and d_move[g] = the proof's move: root WIN, the action of the
+ * WIN edge with the fewest plies; root LOSS, that of the LOSS edge with the most plies; ties to the
+ * lowest slot; otherwise 0xFFFF.  After an advance it reports the kept root's proof.  Fails on a
+ * tree without the solver and while a selection is pending.
+ * gc_tree_root_policy, flags bit 1 (accepted on a solver tree; an error on any other): d_actions /
+ * d_visits / d_pi / d_value are unchanged (the training target stays the visit distribution), only
+ * d_pick changes.  Root WIN: gc_tree_root_proof's move.  Otherwise the candidates are the edges
+ * that are not LOSS; without one, the LOSS edge with the most plies, ties to the lowest slot;
+ * otherwise the pick is made among the candidates only: greedy, the most visited candidate, ties to
+ * the lowest slot; sampled, the integer rule above with total and the prefix taken over the
+ * candidates' visits in slot order; when the candidates' visits sum to 0, the lowest candidate slot
+ * if the root has any visit, else 0xFFFF.
+ * gc_tree_batch_reserve, gc_tree_select_batch and gc_tree_backup_batch fail on a solver tree with
+ * a message that says so: the order in which several descents of one batch prove things needs a
+ * contract of its own. */
 #define GC_TREE_ARRAYS 16
 #define GC_TREE_BATCH_ARRAYS 6
+#define GC_TREE_SOLVER_ARRAYS 5
 typedef struct gc_tree gc_tree;
 int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out);
 int gc_tree_destroy(gc_tree* t);
@@ -501,6 +568,9 @@ int gc_tree_select_batch(gc_tree* t, int leaves, float c_puct, float fpu, float 
 int gc_tree_backup_batch(gc_tree* t, const float* d_value, const uint8_t* d_done, const uint8_t* d_reason,
                          const uint16_t* d_actions, const float* d_priors, const int32_t* d_count, int pri_cap);
 int gc_tree_batch_pointers(gc_tree* t, void** out, int n);
+int gc_tree_solver_enable(gc_tree* t);
+int gc_tree_solver_pointers(gc_tree* t, void** out, int n);
+int gc_tree_root_proof(gc_tree* t, uint8_t* d_status, uint16_t* d_plies, uint16_t* d_move);
 uint64_t gc_tree_device_bytes(gc_tree* t);
 /* The sample store (gc_replay.h): self-play training samples kept on the device.  Every move a
  * packed position and the root's visit counts are recorded per game; when a game ends its samples

@@ -45,9 +45,25 @@ are derived per G, setting and window: k1_over_single (one K = 1 call against on
 simulation: the same work plus the in-flight traffic) and k8_over_8_single (one K = 8 call against
 eight single simulations).
 
+--solver measures what the solver (gc_tree_solver_enable) costs the single-leaf pair, per
+simulation, on the search measurement's shapes, inputs and windows, three ways: "parent" (another
+checkout of this project, normally the parent commit, given by --parent-root and built there),
+"off" (this checkout, a tree that never enabled the solver) and "on" (this checkout, solver=True).
+Each leg runs in a child process of its own (two builds of the library cannot share one), and the
+legs alternate -- parent, off, on, SOLVER_ROUNDS times -- so that drift of the box falls on all
+three; a child warms up with one run and times REPS runs.  Per leg, setting and window: every
+window's us_per_sim, their median, min and max.  off_within_parent_spread says whether the median
+of "off" lies inside [min, max] of the parent's own windows (it is meant to be the same code);
+on_over_off is the ratio of the medians, reported only.  same_visits: the roots' visit counts of
+"off" equal the parent's (a digest), so the same code also computed the same thing.  For "on" the
+proven nodes, the proven roots and the mean path length at the end of each window are recorded
+(with the bench's 3 % terminal leaves and 8..40 moves per node few proofs climb: the cost measured
+is the extra row per level and the propagation's first step).
+
     python tools/tree_bench.py [--games G] [--nodes N] [--out profiles/tree_search.json]
     python tools/tree_bench.py --advance [--out profiles/tree_advance.json]
     python tools/tree_bench.py --leaves [--out profiles/tree_batch.json]
+    python tools/tree_bench.py --solver --parent-root DIR [--out profiles/tree_solver.json]
 """
 import argparse
 import ctypes
@@ -393,6 +409,114 @@ def leaves_leg(nodes, out_path):
             f.write(line + "\n")
 
 
+# ----------------------------------------------------------------------------- the solver
+SOLVER_ROUNDS = 5
+
+
+def solver_child(G, nodes, solver):
+    """one leg in this process: the search measurement's loop on a tree with the solver on or off"""
+    import hashlib
+
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    sims = nodes
+    env = BatchedChessEnv(G * nodes, device=0, seed=11)
+    L = env._L
+    inp = make_inputs(G, sims)
+
+    def upload(a):
+        v = ctypes.c_void_p()
+        _lib.check(L.gc_device_alloc(env.device, ctypes.c_uint64(a.nbytes), ctypes.byref(v)))
+        _lib.check(L.gc_env_copy(env._h, v.value, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+        return v.value
+
+    d = {k: upload(np.ascontiguousarray(v)) for k, v in inp.items()}
+    tree = env.search_tree(G, nodes, cap=CAP, solver=True) if solver else env.search_tree(G, nodes, cap=CAP)
+    sel = tree._sel.ptr
+    res = {"tree_bytes": tree.device_bytes()}
+
+    def block(s):
+        return (d["actions"] + 2 * G * CAP * s, d["priors"] + 4 * G * CAP * s, d["count"] + 4 * G * s, CAP)
+
+    wins = windows(sims)
+    starts = {a: w for w, (a, b) in wins.items()}
+    ends = {b: w for w, (a, b) in wins.items()}
+    for name, (c_puct, fpu) in SETTINGS.items():
+        times = {w: [] for w in wins}
+        out = {}
+        for rep in range(REPS + 1):  # the first run warms up; the trees and so the work are the same every run
+            _lib.check(L.gc_tree_reset(tree._h, *block(sims), None))
+            for s in range(sims):
+                if s in starts:
+                    env.synchronize()
+                    env.record_event(4)
+                _lib.check(L.gc_tree_select(tree._h, c_puct, fpu, sel["parent"], sel["child"], sel["action"]))
+                _lib.check(L.gc_tree_backup(tree._h, d["value"] + 4 * G * s, d["done"] + G * s, d["reason"] + G * s,
+                                            *block(s)))
+                if s + 1 in ends:
+                    w = ends[s + 1]
+                    env.record_event(5)
+                    env.synchronize()
+                    a, b = wins[w]
+                    if rep:
+                        times[w].append(env.elapsed_ms(4, 5) * 1e3 / (b - a))
+                    dep = tree.fetch("depth", "n_nodes")
+                    out[w] = {"mean_depth": round(float(dep["depth"].mean()), 2),
+                              "mean_nodes": round(float(dep["n_nodes"].mean()), 1)}
+                    if solver:
+                        pr = tree.fetch("node_proven")["node_proven"]
+                        live = np.arange(nodes)[None, :] < dep["n_nodes"][:, None]
+                        out[w]["proven_nodes_per_game"] = round(float(((pr != 0) & live).sum()) / G, 2)
+                        out[w]["proven_roots"] = int((pr[:, 0] != 0).sum())
+        for w, t in times.items():
+            out[w]["us_per_sim_reps"] = [round(x, 3) for x in t]
+        out["root_visits_sha"] = hashlib.sha256(tree.fetch("edge_visits")["edge_visits"][:, 0].tobytes()).hexdigest()[:16]
+        res[name] = out
+    env.synchronize()
+    tree.close()
+    for p in d.values():
+        L.gc_device_free(env.device, ctypes.c_void_p(p))
+    env.close()
+    print(json.dumps(res), flush=True)
+
+
+def solver_leg(G, nodes, parent_root, out_path):
+    legs = {"parent": ["--solver-child", "off", "--package-root", os.path.abspath(parent_root)],
+            "off": ["--solver-child", "off"], "on": ["--solver-child", "on"]}
+    raw = {k: [] for k in legs}
+    for _ in range(SOLVER_ROUNDS):
+        for leg, extra in legs.items():
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--games", str(G), "--nodes", str(nodes)] + extra,
+                               capture_output=True, text=True)
+            if r.returncode:
+                raise SystemExit(f"the {leg} leg failed:\n{(r.stderr or r.stdout)[-2000:]}")
+            raw[leg].append(json.loads(r.stdout.strip().splitlines()[-1]))
+            print(leg, "done", flush=True)
+    res = {"games": G, "nodes": nodes, "cap": CAP, "sims": nodes, "rounds": SOLVER_ROUNDS, "reps": REPS,
+           "windows": {w: list(ab) for w, ab in windows(nodes).items()},
+           "tree_bytes": {leg: raw[leg][0]["tree_bytes"] for leg in legs}}
+    for name in SETTINGS:
+        out = {"same_visits": len({r[name]["root_visits_sha"] for leg in ("parent", "off") for r in raw[leg]}) == 1}
+        for w in windows(nodes):
+            row = {}
+            for leg in legs:
+                t = [x for r in raw[leg] for x in r[name][w]["us_per_sim_reps"]]
+                row[leg] = {"us_per_sim": round(median(t), 3), "min": round(min(t), 3), "max": round(max(t), 3),
+                            "us_per_sim_windows": t}
+                row[leg].update({k: v for k, v in raw[leg][-1][name][w].items() if k != "us_per_sim_reps"})
+            row["off_within_parent_spread"] = row["parent"]["min"] <= row["off"]["us_per_sim"] <= row["parent"]["max"]
+            row["off_over_parent"] = round(row["off"]["us_per_sim"] / row["parent"]["us_per_sim"], 4)
+            row["on_over_off"] = round(row["on"]["us_per_sim"] / row["off"]["us_per_sim"], 4)
+            out[w] = row
+        res[name] = out
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+
+
 # ----------------------------------------------------------------------------- the device leg
 def main():
     ap = argparse.ArgumentParser()
@@ -402,10 +526,24 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--advance", action="store_true", help="measure gc_tree_advance (see the module text)")
     ap.add_argument("--leaves", action="store_true", help="measure the batched calls (see the module text)")
+    ap.add_argument("--solver", action="store_true", help="measure the solver's cost (see the module text)")
+    ap.add_argument("--parent-root", default=None, help="--solver: another checkout of the project, built")
     ap.add_argument("--torch-leg", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--solver-child", default=None, choices=("off", "on"), help=argparse.SUPPRESS)
+    ap.add_argument("--package-root", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     G, nodes = args.games, args.nodes
     sims = nodes
+    if args.solver_child:
+        if args.package_root:  # (ahead of this checkout's package)
+            sys.path.insert(0, os.path.join(args.package_root, "gym-chess_amd"))
+        solver_child(G, nodes, args.solver_child == "on")
+        return
+    if args.solver:
+        if not args.parent_root:
+            ap.error("--solver needs --parent-root")
+        solver_leg(G, nodes, args.parent_root, args.out)
+        return
     if args.torch_leg:
         torch_leg(args.torch_leg, G, nodes, sims)
         return
