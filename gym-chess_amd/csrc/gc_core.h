@@ -1699,6 +1699,52 @@ GC_HD void apply_legal_with(Pos& s, bool white, int action, int* reward, bool* i
     clear = cs ? (cw ? (u32)(M_WKC | M_WQC) : (u32)(M_BKC | M_BQC)) : clear;
     s.meta = (s.meta & ~clear) ^ M_WHITE;  // current_player = other (lib.rs:778-780)
 }
+// apply_legal_with in two halves that share nothing but the action's masks (the fused ply runs
+// them on two waves): the king / rook / colour boards and the meta word here, the other four
+// boards, the captured value and the irreversible flag below.  Together they equal
+// apply_legal_with for every action it takes (tests/test_apply_split.py); each writes only its
+// own members of s.
+struct ApplyMasks {
+    bool cs, cw;         // a castle, a white one
+    u64 fm, tm, clr;     // from / to (0 for a castle), the squares kept
+    u64 ck, cr;          // a castle's king and rook targets
+};
+GC_HD ApplyMasks apply_masks(int action) {
+    const bool cs = action >= 4096;
+    const bool cw = action == A_KSW || action == A_QSW, cks = action == A_KSW || action == A_KSB;
+    const int base = cw ? 56 : 0;
+    const u64 cclr = cks ? (0xFull << (base + 4)) : (0x1Full << base);
+    const u64 ck = cs ? bit(base + (cks ? 6 : 2)) : 0ull, cr = cs ? bit(base + (cks ? 5 : 3)) : 0ull;
+    const u64 fm = cs ? 0ull : bit((action >> 6) & 63), tm = cs ? 0ull : bit(action & 63);
+    return ApplyMasks{cs, cw, fm, tm, cs ? ~cclr : ~(fm | tm), ck, cr};
+}
+#define GC_MV(X) s.X = (s.X & m.clr) | ((s.X & m.fm) ? m.tm : 0ull)
+// k, r, w and meta (kw, rw: s.k & s.w, s.r & s.w before the move)
+GC_HD void apply_legal_krw(Pos& s, int action, u64 kw, u64 rw) {
+    const ApplyMasks m = apply_masks(action);
+    const int f = (action >> 6) & 63;
+    const bool wk = (kw & m.fm) != 0, wr = (rw & m.fm) != 0;
+    GC_MV(k); GC_MV(r); GC_MV(w);
+    s.k |= m.ck;
+    s.r |= m.cr;
+    s.w |= m.cw ? (m.ck | m.cr) : 0ull;
+    u32 clear = (wk ? (u32)(M_WKC | M_WQC) : 0u) | ((wr && (f & 7) == 0) ? (u32)M_WQC : 0u) |
+                ((wr && (f & 7) == 7) ? (u32)M_WKC : 0u);
+    clear = m.cs ? (m.cw ? (u32)(M_WKC | M_WQC) : (u32)(M_BKC | M_BQC)) : clear;
+    s.meta = (s.meta & ~clear) ^ M_WHITE;
+}
+// q, b, n, p, the captured value and the irreversible flag (occ0: occ_of(s) before the move;
+// reads s.r for the value)
+GC_HD void apply_legal_qbnp(Pos& s, int action, int* reward, bool* irrev, u64 occ0) {
+    const ApplyMasks m = apply_masks(action);
+    const int t = action & 63;
+    const int v = 10 * (int)((s.q >> t) & 1) + 5 * (int)((s.r >> t) & 1) + 3 * (int)(((s.b | s.n) >> t) & 1) +
+                  (int)((s.p >> t) & 1);
+    *reward = m.cs ? 0 : v;
+    *irrev = !m.cs && (((s.p & m.fm) != 0) || ((occ0 & m.tm) != 0));
+    GC_MV(q); GC_MV(b); GC_MV(n); GC_MV(p);
+}
+#undef GC_MV
 GC_HD void apply_legal(Pos& s, bool white, int action, int* reward, bool* irrev) {
     apply_legal_with(s, white, action, reward, irrev, occ_of(s), s.k & s.w, s.r & s.w);
 }

@@ -2072,14 +2072,25 @@ __global__ void __launch_bounds__(2 * PAIR_BOARDS * PAIRS_WG) PAIR_ATTR
 // The ply's parallel parts -- the enemy map's three parts, the own slider sets' two halves --
 // go to their own waves, so each wave's chain is shorter and a SIMD holds four of them:
 //
-//   phase 0   Q0: applies the action (the last ply's pick) -> post-move board to LDS
-//             Q1: the Philox word, the reset table read (its window probe is in flight)
+//   phase 0   Q0: applies the action (the last ply's pick) to kings, rooks, colours, the meta word
+//             Q1: applies it to the other four boards; the capture's value, the irreversible flag
+//             Q3: checks the Philox word made ahead against the settled draw counter
 //   phase 1   Q0: checkers, check mask, pins                   Q1: the mover's own check flag
 //             Q2: enemy leaper + orthogonal slider attacks     Q3: enemy diagonal slider attacks
 //   phase 2   Q0: castles, pawn and knight sets                Q1: the 3-fold commit
 //             Q2: the own rook/queen direction sets, king sets Q3: the bishop/queen ones
 //   phase 3   Q0: the outcome                                  Q1: the outcome, the stores, the
 //             Q2: the pick of the next action                      next ply's window probe
+//             Q3: the next ply's Philox word and reset table read, on the draw counter's usual step
+//
+// Phase 0 is the interval a quad runs on one wave's chain, so it is cut three ways: Q0 and Q1 both
+// resolve the action and each applies it to the boards of its half (gc_core.h apply_legal_krw,
+// apply_legal_qbnp; the halves cross in LDS after the barrier), and the Philox chain runs on Q3
+// while it waits for the ply's last barrier.  The draw counter steps on every ply but the one
+// after which the next side has no move (the stalemate: the driver's no-move reset follows);
+// Q0 publishes the settled counter before that barrier and Q3 makes the wave's words again where
+// a lane's differs -- exact, tests/test_philox_ahead_gpu.py.  With two quads per workgroup (the
+// short launches) phase 0 stays as it was: all of the apply on Q0, the word on Q1 (S0 below).
 //
 // Q0 and Q1 carry the board's state between plies; Q2 and Q3 are stateless (the post-move
 // board and the pins come through LDS) and compute their sets unconditionally -- ignored,
@@ -2129,9 +2140,9 @@ __global__ void __launch_bounds__(2 * PAIR_BOARDS * PAIRS_WG) PAIR_ATTR
 
 struct QuadLds {
     u64 sets[SW_SETS][QUAD_BOARDS];  // the next side's move sets (Q0: pawns / knights, Q2, Q3)
-    u64 ns[NBB][QUAD_BOARDS];        // Q0 -> all: the post-move board (phase 0)
-    u32 nmeta[QUAD_BOARDS];
-    int32_t mr[QUAD_BOARDS];         //           its capture reward
+    u64 ns[NBB][QUAD_BOARDS];        // Q0 (k, r, w), Q1 (q, b, n, p) -> all: the post-move board (phase 0)
+    u32 nmeta[QUAD_BOARDS];          //           (two quads per workgroup: all of it Q0's)
+    int32_t mr[QUAD_BOARDS];         // Q0 -> Q1, two quads per workgroup: its capture reward
     u32 irrev[QUAD_BOARDS];          //           irreversible move
     u64 pin3[3][QUAD_BOARDS];        // Q0 -> Q2, Q3: check mask, pinned, pin rays
     u32 f0[QUAD_BOARDS];             // Q0 -> Q1: the side to move is in check
@@ -2141,10 +2152,11 @@ struct QuadLds {
     u64 cw0[2][QUAD_BOARDS];         // Q0 -> Q2: its sets' byte counts (words 0, 1: pawns, knights)
     u32 part[4][QUAD_BOARDS];        // partial move totals (Q0's holds the castles)
     u32 rep[QUAD_BOARDS];            // Q1 -> Q0: 3-fold count | window length << 8
-    u32 x0[QUAD_BOARDS];             // Q1 -> Q2: the Philox word of the next draw
-    u32 ra[QUAD_BOARDS];             // Q1 -> Q0: the start-position table pick
-    u32 act[QUAD_BOARDS];            // Q0 -> Q1: this ply's action (phase 0)
+    u32 x0[QUAD_BOARDS];             // Q3 (two quads per workgroup: Q1) -> Q2: the Philox word of the next draw
+    u32 ra[QUAD_BOARDS];             // Q3 -> Q0, Q1 (Q1 -> Q0): the start-position table pick
+    u32 act[QUAD_BOARDS];            // Q0 -> Q1, two quads per workgroup: this ply's action (phase 0)
     u32 pick[QUAD_BOARDS];           // Q2 -> Q0: the policy's pick from this ply's move sets (phase 3)
+    u32 d[QUAD_BOARDS];              // Q0 -> Q3: the settled draw counter (phase 3)
     u32 castles[QUAD_BOARDS];        // Q0 -> Q2: the castles (phase 2)
     u64 occ[HTAB / 64][QUAD_BOARDS];  // (OCC) Q1: the window's taken table slots, a bit per slot
     u32 nkey[QUAD_BOARDS];            // (OCC) Q1, phase 1 -> 3: the next board's key if the move stands
@@ -2190,10 +2202,27 @@ struct QuadQ0Pre {
     u32 meta0;
     u64 occ, kw, rw;
 };
+// (S0, quad_ply's short phase 0: the occupancy is then Q1's to hold, for its half of the apply)
+template <bool S0>
 __device__ __forceinline__ QuadQ0Pre quad_q0pre(const Pos& s) {
-    QuadQ0Pre q{(s.meta & ~(u32)M_RIGHTS) | eff_rights(s), occ_of(s), s.k & s.w, s.r & s.w};
-    pin(q.meta0); pin(q.occ); pin(q.kw); pin(q.rw);
+    QuadQ0Pre q{(s.meta & ~(u32)M_RIGHTS) | eff_rights(s), S0 ? 0ull : occ_of(s), s.k & s.w, s.r & s.w};
+    pin(q.meta0); pin(q.kw); pin(q.rw);
+    if (!S0) pin(q.occ);
     return q;
+}
+// Q1's half of the apply needs the occupancy alone
+__device__ __forceinline__ QuadQ0Pre quad_q1pre(const Pos& s) {
+    QuadQ0Pre q{0u, occ_of(s), 0ull, 0ull};
+    pin(q.occ);
+    return q;
+}
+// Q3: the draw's Philox word and the reset table's pick, made a ply ahead
+struct QuadAhead {
+    u32 x0, ra;
+};
+__device__ __forceinline__ void quad_ahead(const PairCtx& C, int i, u32 d, QuadAhead& ah) {
+    ah.x0 = philox_x0(C.seed, (u32)i, d);
+    ah.ra = C.rtable ? (u32)C.racts[scale_rank(ah.x0, C.rtotal)] : (u32)(uint16_t)A_NONE;
 }
 
 // One ply of board i for role R of its quad (RoleC<0..3>).  Q0 / Q1: in/out as pair_ply (s, a,
@@ -2225,10 +2254,10 @@ struct OccQ {
         if (GC_WG_FAIR && (up)) __builtin_amdgcn_s_setprio((x) + 1); \
         else __builtin_amdgcn_s_setprio(x);                   \
     } while (0)
-template <int R, bool OCC>
+template <int R, bool OCC, bool S0>
 __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l, int i, bool live, Pos& s, int& a,
                                             u32& d, DevHist& h, u32& nst, RepProbe& pr, QuadPend& pend, OccQ& oq,
-                                            QuadQ0Pre& q0, bool up = false) {
+                                            QuadQ0Pre& q0, QuadAhead& ah, bool up = false) {
     constexpr bool CARRY = R < 2;  // Q0 / Q1 hold the state
 #ifdef GC_PSTAMPS
     bool pst_loaded = false;  // Q1: the commit loaded a slot beyond the home slot
@@ -2238,17 +2267,29 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     if (R == 2) QSETPRIO(0, up);
     if (GC_WG_FAIR && R == 1) QSETPRIO(2, up);
     if (GC_WG_FAIR && R == 3) QSETPRIO(0, up);
-    if (R == 0) a = pend.resolve(L, l);  // the last ply's action: Q2's pick, or the reset table's
+    if (R == 0 || (S0 && R == 1)) a = pend.resolve(L, l);  // the last ply's action: Q2's pick, or the reset table's
     u32 x0 = 0;
     uint16_t ra = (uint16_t)A_NONE;
-    if (R == 1) {  // phase 0 work first: it does not depend on the action, which Q1 learns after it
+    if (R == 1 && !S0) {  // phase 0 work first: it does not depend on the action, which Q1 learns after it
         x0 = philox_x0(C.seed, (u32)i, d);  // the next draw (independent of the position)
         if (C.rtable) ra = C.racts[scale_rank(x0, C.rtotal)];
         L.x0[l] = x0;
     }
-    if (R == 0) L.act[l] = (u32)a;
+    if (R == 3 && S0) {
+        // the word made ahead (d: the counter it was made from) against the settled counter: it
+        // stands unless the last ply was a stalemate (the counter stayed); then the whole wave
+        // makes its words again from the settled counters -- the same word where they agree
+        const u32 dt = L.d[l];
+        if (__any(dt != d)) {
+            d = dt;
+            quad_ahead(C, i, d, ah);
+        }
+        L.x0[l] = ah.x0;
+        L.ra[l] = ah.ra;
+    }
+    if (R == 0 && !S0) L.act[l] = (u32)a;
     PST(7);  // (GC_PSTAMPS: the segments as in the paired kernel, phase 0 .. wait D)
-    if (R == 1) {
+    if (R == 1 && !S0) {
         pair_barrier();  // (Q1's phase 0 is above; it meets the others' barrier A here)
         a = (int)L.act[l];
     }
@@ -2261,7 +2302,17 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     bool irrev = false;
     Pos ns;
     // ---- phase 0
-    if (R == 0) {
+    if (R == 0 && S0) {  // the apply's king / rook / colour half
+        ns = s;
+        ns.meta = q0.meta0;  // State::new's rights
+        if (mv) apply_legal_krw(ns, a, q0.kw, q0.rw);
+        L.ns[0][l] = ns.k; L.ns[2][l] = ns.r; L.ns[6][l] = ns.w;
+        L.nmeta[l] = ns.meta;
+    } else if (R == 1 && S0) {  // the other four boards, the capture's value, the irreversible flag
+        ns = s;
+        if (mv) apply_legal_qbnp(ns, a, &mr, &irrev, q0.occ);
+        L.ns[1][l] = ns.q; L.ns[3][l] = ns.b; L.ns[4][l] = ns.n; L.ns[5][l] = ns.p;
+    } else if (R == 0) {
         ns = s;
         ns.meta = q0.meta0;  // State::new's rights
         if (mv) apply_legal_with(ns, white, a, &mr, &irrev, q0.occ, q0.kw, q0.rw);
@@ -2272,7 +2323,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         L.irrev[l] = irrev ? 1u : 0u;
     }
     PST(0);
-    if (R != 1) pair_barrier();
+    if (R != 1 || S0) pair_barrier();
     PST(1);
     // ---- phase 1
     Gen g;
@@ -2282,12 +2333,17 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     // the barrier (10 and 12 u64; these two roles carry no state)
     OrthCarry oc{};
     DiagCarry dc{};
-    if (R != 0) {
+    if (R == 0 && S0) {
+        ns.q = L.ns[1][l]; ns.b = L.ns[3][l]; ns.n = L.ns[4][l]; ns.p = L.ns[5][l];
+    } else if (R == 1 && S0) {
+        ns.k = L.ns[0][l]; ns.r = L.ns[2][l]; ns.w = L.ns[6][l];
+        ns.meta = L.nmeta[l];
+    } else if (R != 0) {
         ns.k = L.ns[0][l]; ns.q = L.ns[1][l]; ns.r = L.ns[2][l]; ns.b = L.ns[3][l];
         ns.n = L.ns[4][l]; ns.p = L.ns[5][l]; ns.w = L.ns[6][l];
         ns.meta = L.nmeta[l];
     }
-    if (R == 1) {
+    if (R == 1 && !S0) {
         mr = L.mr[l];
         irrev = L.irrev[l] != 0;
     }
@@ -2391,7 +2447,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
             }
         }
         L.rep[l] = (u32)c | (hl << 8);
-        L.ra[l] = ra;
+        if (!S0) L.ra[l] = ra;
     } else if (R == 2) {  // unconditional: ignored unless generation is due
         u64 T[SW_SETS];
         sw_orth(ns, g, oc, T);
@@ -2441,6 +2497,7 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
             hl = rpk >> 8;
             ra = (uint16_t)L.ra[l];
         } else {
+            if (S0) ra = (uint16_t)L.ra[l];
             h.commit();  // the window write, issued before the outcome
         }
         bool have = false;
@@ -2497,9 +2554,18 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         const int tot = have ? total : (int)C.rtotal;
         d += tot > 0 ? 1u : 0u;
         if (R == 0) {
+            if (S0) L.d[l] = d;
             pend = QuadPend{have, ra};
-            q0 = quad_q0pre(s);  // the next ply's, in the wait for barrier D
+            q0 = quad_q0pre<S0>(s);  // the next ply's, in the wait for barrier D
+        } else if (S0) {
+            pend = QuadPend{have, ra};
+            q0 = quad_q1pre(s);
         }
+    }
+    if (R == 3 && S0) {  // the next ply's word, on the counter's usual step, in the wait for barrier D
+        d += 1u;
+        pin(d);  // (after barrier C: the chain is not to be scheduled into phase 2)
+        quad_ahead(C, i, d, ah);
     }
     PST(6);
     pair_barrier();  // Q2's pick to Q0; LDS free for the next ply
@@ -2546,6 +2612,9 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
                                       const uint16_t* __restrict__ racts, const EnvDev::InitCache* __restrict__ icd,
                                       u32 rinfo, int plies, uint64_t* __restrict__ stats, u64* __restrict__ trace,
                                       int qw, int l, int i, int place) {
+    // the short phase 0 (quad_ply) with one quad per workgroup; the paired form, the short launches',
+    // keeps all of the apply on Q0 and the Philox word on Q1: there the short one costs 4-5 %
+    constexpr bool S0 = QW == ROLL_QUADS_WG;
     QuadLds& L = roll_lds<QW>(qw);
     const bool live = i < nn;
     const int ii = live ? i : nn - 1;  // dead lanes read a valid board, store nothing
@@ -2553,6 +2622,10 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     const PairCtx C = {seed, htab, in_io.hgen, racts, icd, (rinfo >> 16) != 0, rinfo & 0xFFFFu};
     Pos s{};
     u32 ua = 0, g0 = 0, nst = 0, d = 0;
+    if (RR == 3 && S0) {
+        d = in_io.draw[ii];
+        pin(d);
+    }
     if (RR < 2) {
         s = in_io.load(ii);
         ua = in_io.act[ii];
@@ -2576,9 +2649,15 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     // empty (from the launch's start, or at a reset / an irreversible move); until then the board
     // is probed in the table
     OccQ oq{RR == 1 && hl_of(s.meta) == 0, RR == 1, true, false};
-    QuadPend pend{false, (uint16_t)ua};  // Q0: the first ply's action is the env's
+    QuadPend pend{false, (uint16_t)ua};  // Q0 (and Q1): the first ply's action is the env's
     QuadQ0Pre q0{};
-    if (RR == 0) q0 = quad_q0pre(s);
+    if (RR == 0) q0 = quad_q0pre<S0>(s);
+    if (RR == 1 && S0) q0 = quad_q1pre(s);
+    QuadAhead ah{};
+    if (RR == 3 && S0) {  // the first ply's word, from the entry's counter (read back at the ply's top)
+        quad_ahead(C, i, d, ah);
+        L.d[l] = d;
+    }
 #ifdef GC_PSTAMPS
     const unsigned long long g_pst_entry = pst_entry_where();
     unsigned long long rt1 = 0;
@@ -2605,7 +2684,7 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
       const bool up = GC_WG_FAIR && roll_turn<QW>(place, p0 >> GC_TURN_SHIFT);
       const int pe = p0 + TURN < plies ? p0 + TURN : plies;
       for (int p = p0; p < pe; p++) {
-        o = quad_ply<RR, OCC>(L, C, l, i, live, s, a, d, h, nst, pr, pend, oq, q0, up);
+        o = quad_ply<RR, OCC, S0>(L, C, l, i, live, s, a, d, h, nst, pr, pend, oq, q0, ah, up);
         const int played = a;  // (Q0: resolved at the ply's start; Q1: read after its barrier A)
 #ifdef GC_PSTAMPS
         if (p == 0) rt1 = __builtin_amdgcn_s_memrealtime();
