@@ -1,5 +1,5 @@
 // gc_host_tree.h -- gc_tree_*: the batched search tree's handle, its one device allocation (and
-// advance's remap scratch, the batch scratch and the solver's arrays, allocated when first needed) and the launches of gc_tree.h's kernels,
+// advance's remap scratch, the batch scratch, the solver's and Gumbel root search's arrays, allocated when first needed) and the launches of gc_tree.h's kernels,
 // all asynchronous on the tree env's stream.
 #pragma once
 
@@ -19,6 +19,11 @@ struct gc_tree {
     // gc_tree_solver_enable's arrays: one allocation, GC_TREE_SOLVER_ARRAYS arrays in the header's order
     TreeSolverDev v{};
     uint8_t* vslab = nullptr;
+    // gc_tree_gumbel_enable's arrays: one allocation, GC_TREE_GUMBEL_ARRAYS arrays in the header's order
+    TreeGumbelDev u{};
+    uint8_t* uslab = nullptr;
+    size_t ubytes = 0;
+    bool armed = false;  // gc_tree_gumbel_begin ran for this root: select takes the Gumbel rule at level 0
 };
 
 // the arrays' sizes in bytes, in the header's order
@@ -46,6 +51,42 @@ static void tree_solver_sizes(size_t G, size_t nodes, size_t cap, size_t out[GC_
     const size_t s[GC_TREE_SOLVER_ARRAYS] = {e, 2 * e, n, 2 * n, n};
     for (int k = 0; k < GC_TREE_SOLVER_ARRAYS; k++) out[k] = s[k];
 }
+// Gumbel root search's arrays' sizes in bytes, in the header's order
+static void tree_gumbel_sizes(size_t G, size_t cap, size_t considered, size_t sims, size_t out[GC_TREE_GUMBEL_ARRAYS]) {
+    const size_t s[GC_TREE_GUMBEL_ARRAYS] = {4 * G * cap, 4 * G * cap, 4 * G * cap, 2 * (considered + 1) * sims};
+    for (int k = 0; k < GC_TREE_GUMBEL_ARRAYS; k++) out[k] = s[k];
+}
+// The considered visit counts, [considered + 1][sims]: row k is the order in which sequential
+// halving spends `sims` simulations on k considered moves (the header has the rule).
+static std::vector<uint16_t> tree_gumbel_table(int considered, int sims) {
+    std::vector<uint16_t> t((size_t)(considered + 1) * sims, 0);
+    for (int k = 1; k <= considered; k++) {
+        uint16_t* row = t.data() + (size_t)k * sims;
+        if (k == 1) {
+            for (int i = 0; i < sims; i++) row[i] = (uint16_t)i;
+            continue;
+        }
+        int L = 0;
+        while ((1 << L) < k) L++;
+        std::vector<int> n((size_t)k, 0);
+        int r = k, at = 0;
+        while (at < sims) {
+            int e = sims / (L * r);
+            e = e > 1 ? e : 1;
+            for (int i = 0; i < e && at < sims; i++)
+                for (int m = 0; m < r; m++) {
+                    if (at < sims) row[at++] = (uint16_t)n[m];
+                    n[m]++;
+                }
+            r = r / 2 > 2 ? r / 2 : 2;
+        }
+    }
+    return t;
+}
+static const char* const TREE_GUMBEL_NO_SOLVER =
+    "a gumbel tree (gc_tree_gumbel_enable) takes no solver: the two together are not defined yet";
+static const char* const TREE_GUMBEL_NO_BATCH =
+    "a gumbel tree (gc_tree_gumbel_enable) takes one leaf per game per call: the batch calls are not defined for it yet";
 static const char* const TREE_BATCH_PENDING = "a batch is pending: gc_tree_backup_batch first";
 static const char* const TREE_SOLVER_NO_BATCH =
     "a solver tree takes one leaf per game per call: the batch calls are not defined for it yet";
@@ -110,6 +151,7 @@ extern "C" int gc_tree_destroy(gc_tree* t) {
     if (t->remap) (void)hipFree(t->remap);
     if (t->bslab) (void)hipFree(t->bslab);
     if (t->vslab) (void)hipFree(t->vslab);
+    if (t->uslab) (void)hipFree(t->uslab);
     delete t;
     return 0;
 }
@@ -133,6 +175,7 @@ extern "C" int gc_tree_reset(gc_tree* t, const uint16_t* d_actions, const float*
     HIPCHK(hipGetLastError());
     t->pending = false;
     t->batch_pending = 0;
+    t->armed = false;
     return 0;
 }
 
@@ -146,12 +189,15 @@ extern "C" int gc_tree_select(gc_tree* t, float c_puct, float fpu, int32_t* d_pa
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     SRV_QUIESCE(t->e);
     HIPCHK(hipSetDevice(t->e->device));
-    if (t->vslab)
+    if (t->armed)
+        k_tree_select<false, true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(
+            t->d, c_puct, fpu, d_parent, d_child, d_action, t->v, t->u);
+    else if (t->vslab)
         k_tree_select<true><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent,
-                                                                                      d_child, d_action, t->v);
+                                                                                      d_child, d_action, t->v, t->u);
     else
         k_tree_select<false><<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, c_puct, fpu, d_parent,
-                                                                                       d_child, d_action, t->v);
+                                                                                       d_child, d_action, t->v, t->u);
     HIPCHK(hipGetLastError());
     t->pending = true;
     return 0;
@@ -227,6 +273,7 @@ extern "C" int gc_tree_advance(gc_tree* t, const uint16_t* d_move, const uint16_
         a, remap, d_kept, t->d.games, t->d.nodes);
     HIPCHK(hipGetLastError());
     e->policy_ready = false;  // act[] describes the moved boards' earlier positions
+    t->armed = false;  // the root changed: gc_tree_gumbel_begin draws for the new one
     return 0;
 }
 
@@ -269,6 +316,7 @@ extern "C" int gc_tree_pointers(gc_tree* t, void** out, int n) {
 extern "C" int gc_tree_batch_reserve(gc_tree* t, int max_leaves) {
     if (!t) return fail("null tree");
     if (t->vslab) return fail(TREE_SOLVER_NO_BATCH);
+    if (t->uslab) return fail(TREE_GUMBEL_NO_BATCH);
     if (max_leaves < 1 || max_leaves > 64) return fail("max_leaves must be in [1, 64]");
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
@@ -365,6 +413,7 @@ extern "C" int gc_tree_solver_enable(gc_tree* t) {
     if (t->pending) return fail("a selection is pending: gc_tree_backup first");
     if (t->batch_pending) return fail(TREE_BATCH_PENDING);
     if (t->bslab) return fail("a batch scratch is reserved: the batch calls are not defined for a solver tree yet");
+    if (t->uslab) return fail(TREE_GUMBEL_NO_SOLVER);
     gc_env* e = t->e;
     SRV_QUIESCE(e);
     HIPCHK(hipSetDevice(e->device));
@@ -411,6 +460,94 @@ extern "C" int gc_tree_root_proof(gc_tree* t, uint8_t* d_status, uint16_t* d_pli
     HIPCHK(hipSetDevice(t->e->device));
     k_tree_root_proof<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->v, d_status, d_plies, d_move);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gc_tree_gumbel_enable(gc_tree* t, int considered, int sims, float c_visit, float c_scale) {
+    if (!t) return fail("null tree");
+    if (considered < 1 || considered > t->d.cap) return fail("gumbel: considered must be in [1, cap]");
+    if (sims < 1 || sims > 65535) return fail("gumbel: sims must be in [1, 65535]");
+    if (!std::isfinite(c_visit) || c_visit < 0.f) return fail("gumbel: c_visit must be finite and >= 0");
+    if (!std::isfinite(c_scale) || !(c_scale > 0.f)) return fail("gumbel: c_scale must be finite and > 0");
+    if (t->pending) return fail("gumbel: a selection is pending: gc_tree_backup first");
+    if (t->batch_pending) return fail(TREE_BATCH_PENDING);
+    if (t->vslab) return fail("gumbel: the tree has the solver enabled: the two together are not defined yet");
+    if (t->bslab) return fail("gumbel: a batch scratch is reserved: the batch calls are not defined for a gumbel tree yet");
+    TreeGumbelDev& u = t->u;
+    if (t->uslab && u.considered == considered && u.sims == sims && u.c_visit == c_visit && u.c_scale == c_scale)
+        return 0;
+    gc_env* e = t->e;
+    SRV_QUIESCE(e);
+    HIPCHK(hipSetDevice(e->device));
+    const TreeDev& d = t->d;
+    size_t sz[GC_TREE_GUMBEL_ARRAYS], off[GC_TREE_GUMBEL_ARRAYS], total = 0;
+    tree_gumbel_sizes((size_t)d.games, (size_t)d.cap, (size_t)considered, (size_t)sims, sz);
+    for (int k = 0; k < GC_TREE_GUMBEL_ARRAYS; k++) {
+        off[k] = total;
+        total += (sz[k] + 255) & ~(size_t)255;
+    }
+    uint8_t* slab = nullptr;
+    if (dalloc(&slab, total)) return -1;
+    const std::vector<uint16_t> table = tree_gumbel_table(considered, sims);
+    hipError_t rc = hipMemsetAsync(slab, 0, total, e->stream);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(slab + off[3], table.data(), sz[3], hipMemcpyHostToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);  // (the host table lives until here)
+    if (rc != hipSuccess) {
+        (void)hipFree(slab);
+        return fail(std::string("gumbel: the arrays' upload: ") + hipGetErrorString(rc));
+    }
+    if (t->uslab) {
+        (void)hipFree(t->uslab);  // (waits for the device: no launch still uses the old arrays)
+        t->bytes -= t->ubytes;
+    }
+    t->uslab = slab;
+    t->ubytes = total;
+    t->bytes += total;
+    t->armed = false;
+    u.gumbel = (float*)(slab + off[0]);
+    u.logit = (float*)(slab + off[1]);
+    u.base_visits = (int32_t*)(slab + off[2]);
+    u.table = (const uint16_t*)(slab + off[3]);
+    u.considered = considered;
+    u.sims = sims;
+    u.c_visit = c_visit;
+    u.c_scale = c_scale;
+    return 0;
+}
+
+extern "C" int gc_tree_gumbel_begin(gc_tree* t, uint64_t seed, uint32_t draw) {
+    if (!t) return fail("null tree");
+    if (!t->uslab) return fail("no gumbel search: gc_tree_gumbel_enable first");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    k_tree_gumbel_begin<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->u, seed, draw);
+    HIPCHK(hipGetLastError());
+    t->armed = true;
+    return 0;
+}
+
+extern "C" int gc_tree_gumbel_policy(gc_tree* t, uint16_t* d_actions, int32_t* d_visits, float* d_pi,
+                                     int32_t* d_target, uint16_t* d_pick, float* d_value) {
+    if (!t) return fail("null tree");
+    if (!t->uslab) return fail("no gumbel search: gc_tree_gumbel_enable first");
+    if (!t->armed) return fail("the gumbel search is not armed: gc_tree_gumbel_begin first (reset and advance disarm)");
+    if (t->pending) return fail("a selection is pending: gc_tree_backup first");
+    SRV_QUIESCE(t->e);
+    HIPCHK(hipSetDevice(t->e->device));
+    const TreeGumbelOut a{d_actions, d_visits, d_pi, d_target, d_pick, d_value};
+    k_tree_gumbel_policy<<<tree_grid(t), dim3(64 * TREE_WAVES), 0, t->e->stream>>>(t->d, t->u, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int gc_tree_gumbel_pointers(gc_tree* t, void** out, int n) {
+    if (!t || !out) return fail("null argument");
+    if (n < 1) return fail("n must be >= 1");
+    if (!t->uslab) return fail("no gumbel search: gc_tree_gumbel_enable first");
+    const TreeGumbelDev& u = t->u;
+    void* p[GC_TREE_GUMBEL_ARRAYS] = {u.gumbel, u.logit, u.base_visits, (void*)u.table};
+    for (int k = 0; k < n && k < GC_TREE_GUMBEL_ARRAYS; k++) out[k] = p[k];
     return 0;
 }
 

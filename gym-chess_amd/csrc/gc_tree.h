@@ -6,7 +6,10 @@
 // k_tree_advance_compact, at the end) (gc_tree_*, include/gymchess.h).  The solver
 // (gc_tree_solver_enable: forced wins, draws and losses proven during the search) is the <true>
 // instantiation of k_tree_reset / select / backup / root_policy / advance_compact, plus
-// tree_propagate and k_tree_root_proof; the <false> instantiations never name its arrays.
+// tree_propagate and k_tree_root_proof; the <false> instantiations never name its arrays.  Gumbel
+// root search (gc_tree_gumbel_enable: Gumbel-top-k, sequential halving, the improved policy) is
+// k_tree_gumbel_begin, the <false, true> instantiation of k_tree_select -- only its level 0 differs
+// -- and k_tree_gumbel_policy; no other instantiation names its arrays.
 //
 // Geometry: G games, `nodes` nodes per game, `cap` child slots per node (1..256).  Node k of game
 // g is board g * nodes + k of the tree env; node 0 is the root.  Edge statistics live with the
@@ -93,6 +96,109 @@ __device__ __forceinline__ double tree_wave_sum(double v) {
 __device__ __forceinline__ unsigned long long tree_wave_max(unsigned long long v) {
     TreeReduceU64::TempStorage ts;
     return __shfl(TreeReduceU64(ts).Reduce(v, hipcub::Max()), 0, 64);
+}
+
+// Gumbel root search's arrays and parameters (gc_tree_gumbel_enable; the header has the rules).
+// Only k_tree_gumbel_begin, k_tree_select<false, true> and k_tree_gumbel_policy name them, so a
+// tree that is not armed runs the code it always ran.
+struct TreeGumbelDev {
+    float* gumbel;          // [G][cap]
+    float* logit;           // [G][cap]
+    int32_t* base_visits;   // [G][cap]
+    const uint16_t* table;  // [considered + 1][sims]: the considered visit count per simulation
+    int considered, sims;
+    float c_visit, c_scale;
+};
+// one lane's slot of the root's rows: chunk 0 arrives in the caller's registers, with the node's
+// other loads; a slot at or past nc holds ev 0, lg -inf
+struct TreeGumbelSlot {
+    int ev;
+    float val, pr, gu, lg;
+    int bv;
+};
+__device__ __forceinline__ TreeGumbelSlot tree_gumbel_load(const TreeDev& T, const TreeGumbelDev& U, int g, int nc,
+                                                           int c, int lane, const TreeGumbelSlot& r0) {
+    if (c == 0) return r0;
+    TreeGumbelSlot r{0, 0.f, 0.f, 0.f, -__builtin_inff(), 0};
+    const int s = c * 64 + lane;
+    if (s < nc) {
+        const size_t o = (size_t)g * T.nodes * T.cap + s, w = (size_t)g * T.cap + s;
+        r.ev = T.edge_visits[o];
+        r.val = T.edge_value[o];
+        r.pr = T.prior[o];
+        r.gu = U.gumbel[w];
+        r.lg = U.logit[w];
+        r.bv = U.base_visits[w];
+    }
+    return r;
+}
+// sigma(qhat) of a slot: the completed Q (the edge's mean, v_mix without a visit) times the scale
+__device__ __forceinline__ float tree_gumbel_sigma(const TreeGumbelSlot& r, float vmix, float scale) {
+    return scale * (r.ev > 0 ? r.val / (float)r.ev : vmix);
+}
+
+// The root's slot under the Gumbel rule (the header's "gc_tree_select on an armed tree"), for the
+// wave of game g; S = the sum of the root's edge_visits, lv = leaf_value[root].  FINAL: the
+// candidates are the slots with the most search visits (gc_tree_gumbel_policy's pick), otherwise
+// those with the table's count.  v_mix's two sums are fp64 (exact for <= 256 fp32 terms but for
+// denormal-sized ones), so v_mix is the rounding of the documented quotient.  -1 with NaN scores or
+// no child.  *vmix and *scale are written for every nc.
+template <bool FINAL>
+__device__ __forceinline__ int tree_gumbel_slot(const TreeDev& T, const TreeGumbelDev& U, int g, int nc, int lane,
+                                                const TreeGumbelSlot& r0, int S, float lv, float* vmix,
+                                                float* scale) {
+    const float ninf = -__builtin_inff();
+    const int chunks = (nc + 63) >> 6;
+    int t = 0, nmax = 0, vmax = 0;
+    double num = 0.0, den = 0.0;
+    for (int c = 0; c < chunks; c++) {
+        const TreeGumbelSlot r = tree_gumbel_load(T, U, g, nc, c, lane, r0);
+        if (c * 64 + lane >= nc) continue;
+        const int v = r.ev - r.bv;
+        t += v;
+        nmax = r.ev > nmax ? r.ev : nmax;
+        vmax = v > vmax ? v : vmax;
+        if (r.ev > 0) {
+            den += (double)r.pr;
+            num += (double)r.pr * ((double)r.val / (double)r.ev);
+        }
+    }
+    TreeReduceI::TempStorage ts;
+    nmax = __builtin_amdgcn_readfirstlane(TreeReduceI(ts).Reduce(nmax, hipcub::Max()));
+    den = tree_wave_sum(den);
+    num = tree_wave_sum(num);
+    const float vm = S > 0 && den != 0.0 ? (float)(((double)lv + (double)S * (num / den)) / (1.0 + (double)S)) : lv;
+    const float sc = (U.c_visit + (float)nmax) * U.c_scale;
+    *vmix = vm;
+    *scale = sc;
+    int want;  // the search visits of a candidate
+    if (FINAL) {
+        want = __builtin_amdgcn_readfirstlane(TreeReduceI(ts).Reduce(vmax, hipcub::Max()));
+    } else {
+        t = tree_wave_sum(t);
+        t = t < 0 ? 0 : t < U.sims ? t : U.sims - 1;
+        const int k = U.considered < nc ? U.considered : nc;
+        want = __builtin_amdgcn_readfirstlane((int)U.table[(size_t)k * U.sims + t]);
+    }
+    bool any = false;
+    for (int c = 0; c < chunks; c++) {
+        const TreeGumbelSlot r = tree_gumbel_load(T, U, g, nc, c, lane, r0);
+        any |= __ballot(c * 64 + lane < nc && r.ev - r.bv == want) != 0;
+    }
+    float best = ninf;
+    int j = -1;
+    for (int c = 0; c < chunks; c++) {
+        const TreeGumbelSlot r = tree_gumbel_load(T, U, g, nc, c, lane, r0);
+        const bool on = c * 64 + lane < nc && (!any || r.ev - r.bv == want);
+        const float x = on ? (r.gu + r.lg) + tree_gumbel_sigma(r, vm, sc) : ninf;
+        const float mx = pol_wave_max(x);
+        const unsigned long long hit = __ballot(on && x == mx);
+        if (hit && (j < 0 || mx > best)) {  // an earlier chunk keeps a tie
+            best = mx;
+            j = c * 64 + (int)__builtin_ctzll(hit);
+        }
+    }
+    return j;
 }
 
 // node `node` of game g (all rows written): its child list = the first min(count, pri_cap, cap)
@@ -221,12 +327,16 @@ __device__ __forceinline__ u32 tree_node_rule(const TreeSolverDev& V, size_t o, 
 // edge scores with Q = +1 / 0 / -1, LOSS edges leave the argmax unless all are LOSS, a node with
 // a WIN edge (only ever the root) takes the proof's slot, and a descent that chooses a proven edge
 // ends at its child (the header's "Select on a solver tree").
-template <bool SOLVER>
+// GUMBEL (an armed tree, never with SOLVER): level 0 takes the slot of tree_gumbel_slot; its three
+// [cap] rows and the root's leaf_value join the loads of the level's round trip (the table entry
+// is one dependent load more, of a few hundred bytes every wave shares).  Every deeper level, the
+// path and the three endings are the code below, unchanged.
+template <bool SOLVER, bool GUMBEL = false>
 __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T, float c_puct, float fpu,
                                                                   int32_t* __restrict__ out_parent,
                                                                   int32_t* __restrict__ out_child,
                                                                   uint16_t* __restrict__ out_action,
-                                                                  const TreeSolverDev V) {
+                                                                  const TreeSolverDev V, const TreeGumbelDev U) {
     const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
     if (g >= T.games) return;
     const float ninf = -__builtin_inff();
@@ -253,6 +363,17 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T
         const float pr0 = in0 ? T.prior[o + lane] : 0.f;
         const int ch0 = in0 ? T.child[o + lane] : -1;
         const u32 ac0 = in0 ? T.action[o + lane] : TREE_NO_ACTION;
+        TreeGumbelSlot g0{};
+        float lv0 = 0.f;
+        if constexpr (GUMBEL) {
+            if (D == 0) {  // (without a branch on the lane, like ep0)
+                const size_t w = (size_t)g * T.cap + (in0 ? lane : 0);
+                g0.gu = U.gumbel[w];
+                g0.lg = U.logit[w];
+                g0.bv = U.base_visits[w];
+                lv0 = T.leaf_value[gb];
+            }
+        }
         if (nc <= 0) break;  // (b) a terminal or childless node: the path ends here
         if (lane >= nc) ev0 = 0;
         const int chunks = (nc + 63) >> 6;
@@ -283,7 +404,16 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_select(const TreeDev T
         }
         float best = ninf;
         int j = -1;
-        if (SOLVER && won) {
+        if (GUMBEL && D == 0) {  // the root of an armed tree
+            if constexpr (GUMBEL) {
+                g0.ev = ev0;
+                g0.val = val0;
+                g0.pr = pr0;
+                if (lane >= nc) g0.lg = ninf;
+                float vmix, scale;
+                j = tree_gumbel_slot<false>(T, U, g, nc, lane, g0, total, lv0, &vmix, &scale);
+            }
+        } else if (SOLVER && won) {
             j = tree_proof_slot(V, o, nc, TREE_WIN, lane);
         } else {
             {
@@ -783,6 +913,110 @@ __global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_root_proof(const TreeD
         if (out_status) out_status[g] = (uint8_t)st;
         if (out_plies) out_plies[g] = V.node_plies[nb];
         if (out_move) out_move[g] = slot >= 0 ? T.action[o + slot] : (uint16_t)TREE_NO_ACTION;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gumbel root search (gc_tree_gumbel_*; the header has the contract).
+// k_tree_gumbel_begin: per root slot j < nc the logit logf(prior), the Gumbel variate of the Philox
+// word (seed, g * 256 + j, draw) and the visits the root already has; the padding 0 / -inf / 0.
+// u = (n + 0.5) * 2^-24 with n the word's top 24 bits lies in (0, 1); n + 0.5 is exact in fp32 only
+// below 2^23, so the upper half goes through 1 - u = (2^24 - n - 0.5) * 2^-24, which is exact there,
+// and log1pf: no u rounds to 1 (a variate of +inf) and -log u keeps its relative accuracy near 1.
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_gumbel_begin(const TreeDev T, const TreeGumbelDev U,
+                                                                        u64 seed, u32 draw) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const size_t o = (size_t)g * T.nodes * T.cap, w = (size_t)g * T.cap;
+    int nc = __builtin_amdgcn_readfirstlane(T.n_children[(size_t)g * T.nodes]);
+    nc = nc < T.cap ? nc : T.cap;
+    for (int s = lane; s < T.cap; s += 64) {
+        const bool on = s < nc;
+        const float pr = on ? T.prior[o + s] : 0.f;
+        const int ev = on ? T.edge_visits[o + s] : 0;
+        const u32 n = philox_x0(seed, (u32)g * 256u + (u32)s, draw) >> 8;
+        const float nl = n < (1u << 23) ? -logf(((float)n + 0.5f) * 0x1p-24f)
+                                        : -log1pf(-(((float)((1u << 24) - n) - 0.5f) * 0x1p-24f));
+        U.gumbel[w + s] = on ? -logf(nl) : 0.f;
+        U.logit[w + s] = logf(pr);  // (the padding's prior 0: -inf)
+        U.base_visits[w + s] = ev;
+    }
+}
+
+struct TreeGumbelOut {  // every array may be NULL
+    uint16_t* actions;  // [G][cap]
+    int32_t* visits;    // [G][cap]
+    float* pi;          // [G][cap]
+    int32_t* target;    // [G][cap]
+    uint16_t* pick;     // [G]
+    float* value;       // [G]
+};
+
+// the improved policy softmax(logit + sigma(completed Q)) over the root's children, its fixed-point
+// form for the sample store, v_mix and the move: the best score among the most searched slots
+__global__ __launch_bounds__(64 * TREE_WAVES) void k_tree_gumbel_policy(const TreeDev T, const TreeGumbelDev U,
+                                                                         const TreeGumbelOut A) {
+    const int lane = threadIdx.x & 63, g = blockIdx.x * TREE_WAVES + (threadIdx.x >> 6);
+    if (g >= T.games) return;
+    const float ninf = -__builtin_inff();
+    const size_t nb = (size_t)g * T.nodes, o = nb * T.cap, w = (size_t)g * T.cap;
+    int nc = __builtin_amdgcn_readfirstlane(T.n_children[nb]);
+    nc = nc < T.cap ? nc : T.cap;
+    const float lv = T.leaf_value[nb];
+    TreeGumbelSlot r0{0, 0.f, 0.f, 0.f, ninf, 0};
+    if (lane < nc) {
+        r0.ev = T.edge_visits[o + lane];
+        r0.val = T.edge_value[o + lane];
+        r0.pr = T.prior[o + lane];
+        r0.gu = U.gumbel[w + lane];
+        r0.lg = U.logit[w + lane];
+        r0.bv = U.base_visits[w + lane];
+    }
+    constexpr int CH = TREE_MAX_CAP / 64;
+    int ev[CH];
+    int S = 0;
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+        ev[c] = c * 64 < nc ? tree_gumbel_load(T, U, g, nc, c, lane, r0).ev : 0;
+        S += ev[c];
+    }
+    S = tree_wave_sum(S);
+    float vmix, scale;
+    int j = tree_gumbel_slot<true>(T, U, g, nc, lane, r0, S, lv, &vmix, &scale);
+    if (j < 0 && nc > 0) j = 0;  // (only with NaN scores: some slot, in bounds)
+    // x = logit + sigma, its maximum, exp(x - max) and their sum (fp64: the order of the lanes'
+    // partial sums does not show in the result)
+    float x[CH], m = ninf;
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+        x[c] = ninf;
+        if (c * 64 >= nc) continue;
+        const TreeGumbelSlot r = tree_gumbel_load(T, U, g, nc, c, lane, r0);
+        if (c * 64 + lane < nc) x[c] = r.lg + tree_gumbel_sigma(r, vmix, scale);
+        m = fmaxf(m, x[c]);
+    }
+    m = pol_wave_max(m);
+    double sum = 0.0;
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+        x[c] = c * 64 + lane < nc && m > ninf ? expf(x[c] - m) : 0.f;
+        sum += (double)x[c];
+    }
+    sum = tree_wave_sum(sum);
+    const float total = (float)sum;
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+        const int s = c * 64 + lane;
+        if (s >= T.cap) continue;
+        const float p = total > 0.f ? x[c] / total : 0.f;
+        if (A.actions) A.actions[w + s] = s < nc ? T.action[o + s] : (uint16_t)TREE_NO_ACTION;
+        if (A.visits) A.visits[w + s] = ev[c];
+        if (A.pi) A.pi[w + s] = p;
+        if (A.target) A.target[w + s] = (int32_t)(p * 1048576.0f + 0.5f);
+    }
+    if (lane == 0) {
+        if (A.pick) A.pick[g] = j >= 0 ? T.action[o + j] : (uint16_t)TREE_NO_ACTION;
+        if (A.value) A.value[g] = vmix;
     }
 }
 

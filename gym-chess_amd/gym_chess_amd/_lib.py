@@ -107,6 +107,10 @@ SIGNATURES = {
     "gc_tree_solver_enable": (_I, [_P]),
     "gc_tree_solver_pointers": (_I, [_P, _P, _I]),
     "gc_tree_root_proof": (_I, [_P, _P, _P, _P]),
+    "gc_tree_gumbel_enable": (_I, [_P, _I, _I, ctypes.c_float, ctypes.c_float]),
+    "gc_tree_gumbel_begin": (_I, [_P, _U64, ctypes.c_uint32]),
+    "gc_tree_gumbel_policy": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "gc_tree_gumbel_pointers": (_I, [_P, _P, _I]),
     "gc_tree_device_bytes": (_U64, [_P]),
     "gc_replay_create": (_I, [_P, _I, _I, _I, ctypes.c_int64, _P]),
     "gc_replay_destroy": (_I, [_P]),

@@ -892,6 +892,15 @@ class _DeviceArrays:
         self.ptr = {}
 
 
+class _GumbelPolicy(_DeviceArrays):
+    """gumbel_policy()'s buffers: a root_policy()-like result whose training target is `target`
+    (the improved policy in units of 2^-20) where root_policy's is `visits`"""
+
+    @property
+    def gumbel(self):
+        return True
+
+
 class SearchTree:
     """The batched search tree on the device (gc_tree_*, gym-chess_amd/csrc/gc_tree.h): per game a
     PUCT tree whose child lists are policy_priors' rows.  Every call is one launch, asynchronous on
@@ -935,16 +944,28 @@ class SearchTree:
         root_policy(..., proof=True) the pick plays a proven win, and otherwise never a move that
                                      is proven lost while another is not; the other outputs are unchanged
 
-    ptr[...] are the device addresses of the tree's arrays (ARRAYS, BATCH_ARRAYS once reserved and
-    SOLVER_ARRAYS once enabled), fetch(*keys) host copies (no keys: ARRAYS)."""
+    Gumbel root search (enable_gumbel(); gc_tree_gumbel_*): for few simulations per move.  The
+    root's moves get Gumbel noise once per move, select spends the simulations on the best
+    `considered` of them by sequential halving (deeper levels stay PUCT), and the training target is
+    the improved policy softmax(logit + sigma(completed Q)); one leaf per game per call, no solver:
+
+        enable_gumbel(considered, sims, c_visit, c_scale)   once (again with other parameters: reallocates)
+        gumbel_begin(seed, draw)     once per move, after reset / advance: arms the tree
+        gp = gumbel_policy()         after the simulations: gp.actions / visits / pi / target / pick /
+                                     value (device pointers, .fetch()); store.record(gp) records target
+
+    ptr[...] are the device addresses of the tree's arrays (ARRAYS, BATCH_ARRAYS once reserved,
+    SOLVER_ARRAYS and GUMBEL_ARRAYS once enabled), fetch(*keys) host copies (no keys: ARRAYS)."""
 
     ARRAYS = ("action", "prior", "child", "edge_visits", "edge_value", "n_children", "parent", "parent_slot",
               "leaf_value", "terminal", "n_nodes", "overflow", "depth", "leaf", "leaf_new", "path")
     BATCH_ARRAYS = ("inflight", "b_path", "b_depth", "b_leaf", "b_kind", "collisions")
     SOLVER_ARRAYS = ("edge_proven", "edge_plies", "node_proven", "node_plies", "complete")
+    GUMBEL_ARRAYS = ("gumbel", "logit", "base_visits", "table")
     _DTYPES = {"action": np.uint16, "prior": np.float32, "edge_value": np.float32, "leaf_value": np.float32,
                "terminal": np.uint8, "inflight": np.uint8, "edge_proven": np.uint8, "edge_plies": np.uint16,
-               "node_proven": np.uint8, "node_plies": np.uint16, "complete": np.uint8}
+               "node_proven": np.uint8, "node_plies": np.uint16, "complete": np.uint8, "gumbel": np.float32,
+               "logit": np.float32, "table": np.uint16}
 
     def __init__(self, env, games, nodes, cap=64, solver=False):
         self.env, self.games, self.nodes, self.cap = env, int(games), int(nodes), int(cap)
@@ -969,6 +990,8 @@ class SearchTree:
         self._batch = 0  # leaves per game of the pending batch
         self.solver = False
         self._proof = None  # root_proof()'s buffers, made by enable_solver()
+        self.gumbel = None  # enable_gumbel()'s (considered, sims, c_visit, c_scale)
+        self._gpol = None  # gumbel_policy()'s buffers, made by enable_gumbel()
         if solver:
             self.enable_solver()
 
@@ -985,6 +1008,42 @@ class SearchTree:
                                                    "move": (np.uint16, (G,))})
         self.solver = True
 
+    def enable_gumbel(self, considered=16, sims=32, c_visit=50.0, c_scale=1.0):
+        """turns Gumbel root search on (gc_tree_gumbel_enable: only while nothing is pending, on a
+        tree without the solver and without a batch scratch; again with other parameters it
+        reallocates and disarms); its arrays join ptr[...] / fetch()"""
+        considered, sims = int(considered), int(sims)
+        _lib.check(self._L.gc_tree_gumbel_enable(self._h, considered, sims, float(c_visit), float(c_scale)))
+        addr = (ctypes.c_void_p * len(self.GUMBEL_ARRAYS))()
+        _lib.check(self._L.gc_tree_gumbel_pointers(self._h, addr, len(self.GUMBEL_ARRAYS)))
+        self.ptr.update({k: addr[i] for i, k in enumerate(self.GUMBEL_ARRAYS)})
+        if self._gpol is None:
+            G, C_ = self.games, self.cap
+            self._gpol = _GumbelPolicy(self.env, {"actions": (np.uint16, (G, C_)), "visits": (np.int32, (G, C_)),
+                                                  "pi": (np.float32, (G, C_)), "target": (np.int32, (G, C_)),
+                                                  "pick": (np.uint16, (G,)), "value": (np.float32, (G,))})
+        self.gumbel = (considered, sims, float(c_visit), float(c_scale))
+
+    def gumbel_begin(self, seed=None, draw=0):
+        """once per move, after reset / advance (gc_tree_gumbel_begin): the roots' logits, their
+        Gumbel variates from the Philox stream (seed, game * 256 + slot, draw) (seed None = the
+        env's; the caller advances draw) and the visits a kept root already has; arms the tree"""
+        _lib.check(self._L.gc_tree_gumbel_begin(self._h, ctypes.c_uint64(self.env.seed if seed is None else int(seed)),
+                                                int(draw) & 0xFFFFFFFF))
+
+    def gumbel_policy(self):
+        """after the move's simulations (gc_tree_gumbel_policy): the roots' actions uint16[G][cap],
+        visits int32[G][cap], the improved policy pi float32[G][cap] and target int32[G][cap] (pi
+        in units of 2^-20: what a sample store records), the move pick uint16[G] (the best score
+        among the most searched moves) and value float32[G] (v_mix); returns the tree's buffers
+        (device pointers as attributes, .fetch(), .gumbel True)"""
+        if self._gpol is None:
+            raise ValueError("gumbel_policy: enable_gumbel() first")
+        r = self._gpol.ptr
+        _lib.check(self._L.gc_tree_gumbel_policy(self._h, r["actions"], r["visits"], r["pi"], r["target"], r["pick"],
+                                                 r["value"]))
+        return self._gpol
+
     def root_proof(self):
         """the roots' proofs (gc_tree_root_proof): status uint8[G] (0 unknown, 1 WIN, 2 DRAW, 3
         LOSS for the side to move), plies uint16[G] and move uint16[G] (the fastest win / the
@@ -1000,6 +1059,8 @@ class SearchTree:
         G, N, C_ = self.games, self.nodes, self.cap
         if k in self.SOLVER_ARRAYS:
             return (G, N, C_) if k.startswith("edge_") else (G, N)
+        if k in self.GUMBEL_ARRAYS:
+            return (self.gumbel[0] + 1, self.gumbel[1]) if k == "table" else (G, C_)
         if k in self.BATCH_ARRAYS:
             K = self.max_leaves
             return {"inflight": (G, N, C_), "b_path": (G, K, N, 2), "collisions": (G,)}.get(k, (G, K))
@@ -1164,6 +1225,9 @@ class SearchTree:
             if self._proof is not None:
                 self._proof.close()
                 self._proof = None
+            if self._gpol is not None:
+                self._gpol.close()
+                self._gpol = None
             self.ptr = {}
 
     def __del__(self):
@@ -1180,7 +1244,8 @@ class SampleStore:
 
         record(root)                 before the move is played: the board's packed position and the
                                      root's (action, visits) list become the game's next pending
-                                     sample (root: a tree's root_policy() result, or (actions_ptr,
+                                     sample (root: a tree's root_policy() result, a gumbel_policy()
+                                     result -- its target takes the visits' place --, or (actions_ptr,
                                      visits_ptr, row_cap)); games whose visits sum to 0 are skipped
         commit(io)                   after the step: every finished game's pending samples get z --
                                      +1 / -1 / 0 from the step's reason (or `outcome`), alternating
@@ -1231,7 +1296,8 @@ class SampleStore:
     def record(self, root):
         """the positions before the move and the roots' visit counts (gc_replay_record)"""
         if isinstance(root, _DeviceArrays):
-            a, v, rc = root.ptr["actions"], root.ptr["visits"], root._spec["actions"][1][-1]
+            v = root.ptr["target" if getattr(root, "gumbel", False) else "visits"]
+            a, rc = root.ptr["actions"], root._spec["actions"][1][-1]
         else:
             a, v, rc = root
         _lib.check(self._L.gc_replay_record(self._h, int(a), int(v), int(rc)))

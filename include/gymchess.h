@@ -545,10 +545,67 @@ int gc_env_clone_errors(gc_env* dst, uint64_t* skipped);
  * if the root has any visit, else 0xFFFF.
  * gc_tree_batch_reserve, gc_tree_select_batch and gc_tree_backup_batch fail on a solver tree with
  * a message that says so: the order in which several descents of one batch prove things needs a
- * contract of its own. */
+ * contract of its own.
+ * Gumbel root search (Danihelka et al., "Policy improvement by planning with Gumbel"): an opt-in
+ * mode of a handle for few simulations per move.  The considered moves are sampled without
+ * replacement by the Gumbel-top-k trick, the budget is spent on them by sequential halving, and the
+ * training target is softmax(logits + sigma(completed Q)).  Only what gc_tree_select does at the
+ * root changes; a tree that never calls gc_tree_gumbel_enable behaves exactly as described above.
+ * Below, "root" is node 0 of a game, nc = n_children[root], N_j = edge_visits[root][j].
+ * gc_tree_gumbel_enable(considered, sims, c_visit, c_scale): 1 <= considered <= cap, 1 <= sims <=
+ * 65535, c_visit finite and >= 0, c_scale finite and > 0.  One allocation, zero-filled on e's
+ * stream, counted by gc_tree_device_bytes from then on; gc_tree_gumbel_pointers hands the arrays
+ * out in this order (GC_TREE_GUMBEL_ARRAYS of them; the first min(n, GC_TREE_GUMBEL_ARRAYS), n >=
+ * 1); it fails before the mode is enabled:
+ *    0 gumbel      f32 [games][cap]          the root's Gumbel variates of this move
+ *    1 logit       f32 [games][cap]          logf(prior) of the root's children
+ *    2 base_visits i32 [games][cap]          N_j when gc_tree_gumbel_begin ran
+ *    3 table       u16 [considered + 1][sims]  table[k][t] = the visits a considered move must
+ *                                            have to be searched in simulation t of k considered moves
+ * The table is built on the host and uploaded once (the call waits for the upload).  Row 0 is all
+ * zeros, row 1 is 0, 1, 2, ...; for k >= 2, with L = ceil(log2 k), a counter per considered move
+ * (all 0) and r = k moves remaining, until the row holds sims entries: e = max(1, floor(sims / (L *
+ * r))); e times, the first r counters are appended and then incremented; then r = max(2, r / 2).
+ * The row is cut at sims entries (k = 4, sims = 8: 0 0 0 0 1 1 2 2).  Calling enable again with
+ * other parameters reallocates and disarms; with the same parameters it does nothing.  It fails,
+ * with nothing launched and a message that says which, while a selection or batch is pending, on a
+ * tree with the solver enabled and on a tree with a batch scratch reserved; conversely
+ * gc_tree_solver_enable and gc_tree_batch_reserve fail on a gumbel tree with a message that says so.
+ * gc_tree_gumbel_begin(seed, draw): one launch, one wave per game, once per move after reset or
+ * advance.  For j < nc: logit_j = logf(prior_j) (a prior of 0 gives -inf); with n = philox_x0(seed,
+ * g * 256 + j, draw) >> 8, u_j = (n + 0.5) * 2^-24 (never 0 or 1: evaluated as ((float)n + 0.5f) *
+ * 2^-24 below n = 2^23, where that is exact, and through 1 - u_j above) and gumbel_j = -logf(-logf(
+ * u_j)); base_visits_j = N_j (non-zero on a root kept by advance).  Slots >= nc get gumbel 0, logit
+ * -inf, base 0.  The handle becomes ARMED; gc_tree_reset and gc_tree_advance disarm it.  Fails
+ * before enable and while a selection is pending.  A run is a function of (seed, game, draw).
+ * gc_tree_select on an armed tree: only level 0 changes; every deeper level, the path, cases (a) /
+ * (b) / (c), the outputs and gc_tree_backup stay as documented.  At the root, v_j = N_j -
+ * base_visits_j (the visits of this search), t = sum_j v_j, k = min(considered, nc), c =
+ * table[k][min(t, sims - 1)].  The candidates are the slots j < nc with v_j == c; if there is none,
+ * every j < nc.  In fp32, score_j = (gumbel_j + logit_j) + ((c_visit + (float)max_b N_b) * c_scale)
+ * * qhat_j with qhat_j = edge_value_j / N_j when N_j > 0, else v_mix; with S = sum_b N_b, v_mix =
+ * (leaf_value[root] + S * (sum_{N_b > 0} prior_b * q_b) / (sum_{N_b > 0} prior_b)) / (1 + S)
+ * (evaluated in fp64 and rounded once), and v_mix = leaf_value[root] when S == 0 or the prior sum
+ * is 0.  The largest score among the candidates wins, ties go to the lowest slot, NaNs give some
+ * in-bounds slot.  The moves with the `considered` largest gumbel + logit are the ones searched
+ * first, and halving keeps the better half: no list of considered moves is stored.  Values are in
+ * [-1, 1] from the view of the side to move at the root; the paper normalises them to [0, 1], which
+ * is this rule with c_scale halved (the shift cancels in the argmax and in the softmax).  An
+ * enabled tree that is not armed selects with the plain PUCT rule, through the same kernel as a
+ * tree without the mode.
+ * gc_tree_gumbel_policy (one launch; every output may be NULL; fails unless armed and while a
+ * selection is pending): d_actions / d_visits as gc_tree_root_policy's (the full N_j, padding
+ * 0xFFFF / 0); d_pi[g][j] = softmax over j < nc of (logit_j + sigma_j), sigma_j = ((c_visit +
+ * max_b N_b) * c_scale) * qhat_j as above, padding 0, a row with nc == 0 or with every logit -inf
+ * all 0; d_target[g][j] = (int32)(d_pi[g][j] * 1048576.0f + 0.5f), the improved policy in units of
+ * 2^-20 -- the block gc_replay_record takes as its visits, so that gc_replay_sample returns the
+ * improved policy as pi; d_pick[g] = among j < nc with v_j == max_b v_b the largest score_j, ties
+ * to the lowest slot, 0xFFFF when nc == 0 (with no simulation run this is a sample from the prior
+ * by the Gumbel-max trick); d_value[g] = v_mix. */
 #define GC_TREE_ARRAYS 16
 #define GC_TREE_BATCH_ARRAYS 6
 #define GC_TREE_SOLVER_ARRAYS 5
+#define GC_TREE_GUMBEL_ARRAYS 4
 typedef struct gc_tree gc_tree;
 int gc_tree_create(gc_env* e, int games, int nodes, int cap, gc_tree** out);
 int gc_tree_destroy(gc_tree* t);
@@ -571,6 +628,11 @@ int gc_tree_batch_pointers(gc_tree* t, void** out, int n);
 int gc_tree_solver_enable(gc_tree* t);
 int gc_tree_solver_pointers(gc_tree* t, void** out, int n);
 int gc_tree_root_proof(gc_tree* t, uint8_t* d_status, uint16_t* d_plies, uint16_t* d_move);
+int gc_tree_gumbel_enable(gc_tree* t, int considered, int sims, float c_visit, float c_scale);
+int gc_tree_gumbel_begin(gc_tree* t, uint64_t seed, uint32_t draw);
+int gc_tree_gumbel_policy(gc_tree* t, uint16_t* d_actions, int32_t* d_visits, float* d_pi, int32_t* d_target,
+                          uint16_t* d_pick, float* d_value);
+int gc_tree_gumbel_pointers(gc_tree* t, void** out, int n);
 uint64_t gc_tree_device_bytes(gc_tree* t);
 /* The sample store (gc_replay.h): self-play training samples kept on the device.  Every move a
  * packed position and the root's visit counts are recorded per game; when a game ends its samples

@@ -60,10 +60,27 @@ proven nodes, the proven roots and the mean path length at the end of each windo
 (with the bench's 3 % terminal leaves and 8..40 moves per node few proofs climb: the cost measured
 is the extra row per level and the propagation's first step).
 
+--gumbel measures Gumbel root search (gc_tree_gumbel_*), cap 64, 16 considered moves, for G in {1 024,
+32} games and sims in {16, 64}, in a child process per round.  Per G and sims: "search" = a whole
+search from the root, us per simulation (select + backup, one window of `sims` simulations by
+events on the env's stream, no host synchronisation inside), armed (reset, gumbel_begin, the
+simulations) against a plain PUCT search of as many simulations on a tree without the mode -- the
+two grow different trees.  "same_trees" = the armed search's final trees copied into both handles
+(the armed one and the plain one, through the host), then a window of GUMBEL_WINDOW further
+simulations on each: the backup is the same kernel on the same kind of path, so armed - plain is
+what the Gumbel rule adds to a select; the copy is repeated before every timed window.  begin_us /
+policy_us: events around one call, medians of 20.  Every figure is the median over the rounds'
+windows, with min and max.  The same rounds also time the plain single-leaf pair of a tree without
+the mode on the search measurement's shapes ("parent": another checkout, normally the parent
+commit, given by --parent-root and built there; "off": this checkout), alternating, exactly as
+--solver does: off_within_parent_spread says whether this checkout's median lies inside [min,
+max] of the parent's own windows, same_visits that both computed the same root visits.
+
     python tools/tree_bench.py [--games G] [--nodes N] [--out profiles/tree_search.json]
     python tools/tree_bench.py --advance [--out profiles/tree_advance.json]
     python tools/tree_bench.py --leaves [--out profiles/tree_batch.json]
     python tools/tree_bench.py --solver --parent-root DIR [--out profiles/tree_solver.json]
+    python tools/tree_bench.py --gumbel --parent-root DIR [--out profiles/tree_gumbel.json]
 """
 import argparse
 import ctypes
@@ -517,6 +534,145 @@ def solver_leg(G, nodes, parent_root, out_path):
             f.write(line + "\n")
 
 
+# ----------------------------------------------------------------------------- Gumbel root search
+GUMBEL_GAMES = (1024, 32)
+GUMBEL_SIMS = (16, 64)
+GUMBEL_CONSIDERED = 16
+GUMBEL_WINDOW = 16
+GUMBEL_ROUNDS = 5
+
+
+def gumbel_child():
+    """one round in this process: every (G, sims) of the Gumbel measurement"""
+    from gym_chess_amd import _lib
+    from gym_chess_amd.env import BatchedChessEnv
+
+    c_puct, fpu = SETTINGS["broad"]
+    res = {"runs": []}
+    for G in GUMBEL_GAMES:
+        for sims in GUMBEL_SIMS:
+            total = sims + GUMBEL_WINDOW
+            nodes = total + 1
+            env = BatchedChessEnv(G * nodes, device=0, seed=11)
+            L = env._L
+            inp = make_inputs(G, total)
+
+            def upload(a):
+                v = ctypes.c_void_p()
+                _lib.check(L.gc_device_alloc(env.device, ctypes.c_uint64(a.nbytes), ctypes.byref(v)))
+                _lib.check(L.gc_env_copy(env._h, v.value, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+                return v.value
+
+            d = {k: upload(np.ascontiguousarray(v)) for k, v in inp.items()}
+            armed = env.search_tree(G, nodes, cap=CAP)
+            armed.enable_gumbel(GUMBEL_CONSIDERED, sims)
+            plain = env.search_tree(G, nodes, cap=CAP)
+
+            def block(s):
+                return (d["actions"] + 2 * G * CAP * s, d["priors"] + 4 * G * CAP * s, d["count"] + 4 * G * s, CAP)
+
+            def simulate(tree, s):
+                sel = tree._sel.ptr
+                _lib.check(L.gc_tree_select(tree._h, c_puct, fpu, sel["parent"], sel["child"], sel["action"]))
+                _lib.check(L.gc_tree_backup(tree._h, d["value"] + 4 * G * s, d["done"] + G * s, d["reason"] + G * s,
+                                            *block(s)))
+
+            def window(tree, a, b):
+                env.synchronize()
+                env.record_event(4)
+                for s in range(a, b):
+                    simulate(tree, s)
+                env.record_event(5)
+                env.synchronize()
+                return env.elapsed_ms(4, 5) * 1e3 / (b - a)
+
+            t = {k: [] for k in ("search_armed", "search_plain", "same_armed", "same_plain", "begin", "policy")}
+            snap = None
+            for rep in range(REPS + 1):  # the first run warms up; the trees are the same every run
+                _lib.check(L.gc_tree_reset(armed._h, *block(total), None))
+                armed.gumbel_begin(seed=5, draw=0)
+                ta = window(armed, 0, sims)
+                _lib.check(L.gc_tree_reset(plain._h, *block(total), None))
+                tp = window(plain, 0, sims)
+                if snap is None:
+                    snap = armed.fetch()
+                    visits = snap["edge_visits"][:, 0].copy()
+                for tree in (armed, plain):  # the armed search's trees in both handles
+                    for k, a in snap.items():
+                        _lib.check(L.gc_env_copy(env._h, tree.ptr[k], _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+                sa = window(armed, sims, total)
+                sp = window(plain, sims, total)
+                if rep:
+                    for k, x in zip(("search_armed", "search_plain", "same_armed", "same_plain"), (ta, tp, sa, sp)):
+                        t[k].append(round(x, 3))
+            for _ in range(20):
+                env.record_event(0)
+                armed.gumbel_begin(seed=5, draw=1)
+                env.record_event(1)
+                armed.gumbel_policy()
+                env.record_event(2)
+                env.synchronize()
+                t["begin"].append(round(env.elapsed_ms(0, 1) * 1e3, 3))
+                t["policy"].append(round(env.elapsed_ms(1, 2) * 1e3, 3))
+            t["begin"], t["policy"] = [median(t["begin"])], [median(t["policy"])]
+            nc = snap["n_children"][:, 0]
+            res["runs"].append({"games": G, "sims": sims, "nodes": nodes, "times": t,
+                                "searched_moves_mean": round(float((visits > 0).sum(axis=1).mean()), 2),
+                                "root_children_mean": round(float(nc.mean()), 2),
+                                "gumbel_bytes": armed.device_bytes() - plain.device_bytes()})
+            env.synchronize()
+            armed.close()
+            plain.close()
+            for ptr in d.values():
+                L.gc_device_free(env.device, ctypes.c_void_p(ptr))
+            env.close()
+    print(json.dumps(res), flush=True)
+
+
+def gumbel_leg(G, nodes, parent_root, out_path):
+    me = [sys.executable, os.path.abspath(__file__)]
+    plain = me + ["--games", str(G), "--nodes", str(nodes), "--solver-child", "off"]
+    legs = {"parent": plain + ["--package-root", os.path.abspath(parent_root)], "off": plain,
+            "gumbel": me + ["--gumbel-child"]}
+    raw = {k: [] for k in legs}
+    for _ in range(GUMBEL_ROUNDS):
+        for leg, cmd in legs.items():
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode:
+                raise SystemExit(f"the {leg} leg failed:\n{(r.stderr or r.stdout)[-2000:]}")
+            raw[leg].append(json.loads(r.stdout.strip().splitlines()[-1]))
+            print(leg, "done", flush=True)
+
+    def stats(xs):
+        return {"us": round(median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3), "windows": xs}
+
+    res = {"cap": CAP, "considered": GUMBEL_CONSIDERED, "window": GUMBEL_WINDOW, "rounds": GUMBEL_ROUNDS, "reps": REPS,
+           "setting": SETTINGS["broad"], "gumbel": []}
+    for i, run in enumerate(raw["gumbel"][0]["runs"]):
+        row = {k: v for k, v in run.items() if k != "times"}
+        t = {k: stats([x for r in raw["gumbel"] for x in r["runs"][i]["times"][k]]) for k in run["times"]}
+        row.update({"search_us_per_sim": {"armed": t["search_armed"], "plain": t["search_plain"]},
+                    "same_trees_us_per_sim": {"armed": t["same_armed"], "plain": t["same_plain"]},
+                    "armed_select_extra_us": round(t["same_armed"]["us"] - t["same_plain"]["us"], 3),
+                    "begin_us": t["begin"], "policy_us": t["policy"]})
+        res["gumbel"].append(row)
+    plain_res = {"games": G, "nodes": nodes, "sims": nodes, "windows": {w: list(ab) for w, ab in windows(nodes).items()}}
+    for name in SETTINGS:
+        out = {"same_visits": len({r[name]["root_visits_sha"] for leg in ("parent", "off") for r in raw[leg]}) == 1}
+        for w in windows(nodes):
+            row = {leg: stats([x for r in raw[leg] for x in r[name][w]["us_per_sim_reps"]]) for leg in ("parent", "off")}
+            row["off_within_parent_spread"] = row["parent"]["min"] <= row["off"]["us"] <= row["parent"]["max"]
+            row["off_over_parent"] = round(row["off"]["us"] / row["parent"]["us"], 4)
+            out[w] = row
+        plain_res[name] = out
+    res["plain_path"] = plain_res
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(line + "\n")
+
+
 # ----------------------------------------------------------------------------- the device leg
 def main():
     ap = argparse.ArgumentParser()
@@ -527,7 +683,9 @@ def main():
     ap.add_argument("--advance", action="store_true", help="measure gc_tree_advance (see the module text)")
     ap.add_argument("--leaves", action="store_true", help="measure the batched calls (see the module text)")
     ap.add_argument("--solver", action="store_true", help="measure the solver's cost (see the module text)")
-    ap.add_argument("--parent-root", default=None, help="--solver: another checkout of the project, built")
+    ap.add_argument("--gumbel", action="store_true", help="measure Gumbel root search (see the module text)")
+    ap.add_argument("--parent-root", default=None, help="--solver / --gumbel: another checkout of the project, built")
+    ap.add_argument("--gumbel-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--torch-leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--solver-child", default=None, choices=("off", "on"), help=argparse.SUPPRESS)
     ap.add_argument("--package-root", default=None, help=argparse.SUPPRESS)
@@ -538,6 +696,14 @@ def main():
         if args.package_root:  # (ahead of this checkout's package)
             sys.path.insert(0, os.path.join(args.package_root, "gym-chess_amd"))
         solver_child(G, nodes, args.solver_child == "on")
+        return
+    if args.gumbel_child:
+        gumbel_child()
+        return
+    if args.gumbel:
+        if not args.parent_root:
+            ap.error("--gumbel needs --parent-root")
+        gumbel_leg(G, nodes, args.parent_root, args.out)
         return
     if args.solver:
         if not args.parent_root:
