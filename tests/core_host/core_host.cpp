@@ -634,3 +634,39 @@ extern "C" void host_fide_rollout(const int8_t* init, uint64_t seed, uint32_t bo
         tr_reason[p] = (uint8_t)o.reason;
     }
 }
+
+// ---- one external-action step / one engine move under FIDE rules, for tests/fide_ref.py -----
+// env state in: board, meta8 (rights; check flags derived from the board as k_fenv_import does),
+// the en-passant file (-1 none), move_count, the state's done flag.  hist: a window kept across
+// calls (host_fide_hist_new), or NULL for a fresh one.
+extern "C" void* host_fide_hist_new() {
+    HostHist* h = new HostHist();
+    h->bump_gen();
+    return h;
+}
+extern "C" void host_fide_hist_free(void* h) { delete (HostHist*)h; }
+extern "C" void host_fide_step(void* hist, const int8_t* b, const uint8_t* m, int ep, int move_count, int was_done,
+                               int action, int validate, int8_t* ob, uint8_t* om, int* out5) {
+    u32 meta = (m[0] ? M_WHITE : 0u) | (m[1] ? M_WKC : 0u) | (m[2] ? M_WQC : 0u) | (m[3] ? M_BKC : 0u) |
+               (m[4] ? M_BQC : 0u) | ((u32)move_count << M_MC_SHIFT) | (was_done ? (u32)M_DONE : 0u);
+    Pos s = from_mailbox(b, fide::with_ep(meta, ep));
+    s.meta |= fide::fcheck_flags(s);
+    HostHist fresh;
+    if (!hist) fresh.bump_gen();
+    HostHist& h = hist ? *(HostHist*)hist : fresh;
+    fide::FGen f;
+    StepOut o = validate ? fide::fenv_step<true>(s, h, action, f) : fide::fenv_step<false>(s, h, action, f);
+    export_state(s, ob, om);
+    const int file = fide::ep_square(s.meta) >= 0 ? fide::ep_square(s.meta) & 7 : -1;
+    out5[0] = file; out5[1] = o.reward; out5[2] = o.done; out5[3] = o.reason; out5[4] = (s.meta & M_DONE) != 0;
+}
+// fapply + fcheck_flags, as k_fnext_state: engine form (meta8[7] = en-passant file + 1)
+extern "C" int host_fide_next_state(const int8_t* b, const uint8_t* m, int action, int8_t* ob, uint8_t* om, int* reward) {
+    Pos s = fide_import(b, m);
+    bool irrev;
+    int rc = fide::fapply(s, action, 0, reward, &irrev);
+    if (rc == 0) s.meta = (s.meta & ~(u32)(M_WCHK | M_BCHK)) | fide::fcheck_flags(s);
+    export_state(s, ob, om);
+    om[7] = (s.meta & fide::M_EP) ? (uint8_t)(((s.meta & fide::M_EP_MASK) >> fide::M_EP_SHIFT) + 1) : 0;
+    return rc;
+}

@@ -96,6 +96,10 @@ def lib():
         L.host_fide_gen_check.argtypes = [P, P, ctypes.c_int, P, P, P]
         L.host_fide_list.argtypes = [P, P, P, ctypes.c_int]
         L.host_fide_rollout.argtypes = [P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, P, P, P, P]
+        L.host_fide_hist_new.restype = P
+        L.host_fide_hist_free.argtypes = [P]
+        L.host_fide_step.argtypes = [P, P, P] + [ctypes.c_int] * 5 + [P, P, P]
+        L.host_fide_next_state.argtypes = [P, P, ctypes.c_int, P, P, P]
         _L = L
     return _L
 
@@ -251,6 +255,42 @@ def fide_rollout(seed, board_id, plies, init):
     q = np.zeros(plies, dtype=np.uint8)
     lib().host_fide_rollout(_p(init), seed, board_id, plies, _p(a), _p(r), _p(d), _p(q))
     return dict(action=a, reward=r, done=d, reason=q)
+
+
+class FideHist:
+    """a 3-fold window kept across host_fide_step calls (one episode of one board)"""
+
+    def __init__(self):
+        self.h = lib().host_fide_hist_new()
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().host_fide_hist_free(self.h)
+
+
+def host_fide_step(board, meta8, ep, move_count, action, validate=True, hist=None, done=False):
+    """One env step of fide::fenv_step<validate> on the env-form state (meta8's rights, the
+    en-passant file, move_count, the state's done flag; check flags from the board), with a
+    fresh window or `hist`.  -> dict(board, meta8 (meta8[7] = move_count), ep, reward, done,
+    reason, state_done)"""
+    b, m = _bm(board, meta8)
+    ob = np.zeros(64, dtype=np.int8)
+    om = np.zeros(8, dtype=np.uint8)
+    o = np.zeros(5, dtype=np.int32)
+    lib().host_fide_step(hist.h if hist is not None else None, _p(b), _p(m), int(ep), int(move_count), int(bool(done)),
+                         int(action), int(bool(validate)), _p(ob), _p(om), _p(o))
+    return dict(board=ob, meta8=om, ep=int(o[0]), reward=int(o[1]), done=bool(o[2]), reason=int(o[3]),
+                state_done=bool(o[4]))
+
+
+def host_fide_next_state(board, meta8, action):
+    """fapply + fcheck_flags (as k_fnext_state), engine form -> (status, board, meta8, reward)"""
+    b, m = _bm(board, meta8)
+    ob = np.zeros(64, dtype=np.int8)
+    om = np.zeros(8, dtype=np.uint8)
+    rw = ctypes.c_int()
+    rc = lib().host_fide_next_state(_p(b), _p(m), int(action), _p(ob), _p(om), ctypes.byref(rw))
+    return rc, ob, om, rw.value
 
 
 def mover_checked(board, meta, action):

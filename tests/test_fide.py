@@ -1,7 +1,12 @@
 """Optional FIDE rules mode -- OUTSIDE the reference-parity contract.
 
-The reference plays its own rules (gc_core.h); for rules="fide" there is no reference
-implementation, so the pin is the published perft totals: the standard positions of the
+The reference plays its own rules (gc_core.h), so rules="fide" is pinned twice.  The move
+COUNTS are pinned here by the published perft totals; what a trainer consumes -- action ids,
+next states, rights, flags, the en-passant file, rewards, endings, move_count -- is pinned move
+by move to an independent plain-Python reference (tests/fide_ref.py) in tests/test_fide_ref.py
+(host build) and tests/test_fide_ref_gpu.py (device).  The tests of this file that compare the
+device with the host build of the same source, or one kernel with another, show that the
+kernels agree with each other, not that they are right.  The perft positions: the standard positions of the
 chessprogramming.org "Perft Results" page (start position, Kiwipete, positions 3-6) and
 the en-passant / castling / promotion / stalemate edge positions in wide use for testing
 move generators.  CPU tests run the host build of gc_fide.h (tests/core_host); GPU tests
