@@ -1410,10 +1410,16 @@ GC_HD int sw_origin(const Gen& g, int j, int to) {
     // sliders: direction d = j - SW_ORTH; d 1, 2, 6, 7 move toward higher squares
     const int d = (j - SW_ORTH) & 7;
     const bool up = ((0xC6u >> d) & 1) != 0;
-    const u64 line = d < 2 ? file_mask(to) : d < 4 ? row_mask(to) : (d == 5 || d == 6) ? diag_mask(to) : anti_mask(to);
-    const u64 x = g.occ & line;
-    const u64 lo = x & below(to), hi = x & (~below(to) ^ bit(to));
-    const int sl = up ? (lo ? msb(lo) : 0) : (hi ? ctz(hi) : 0);
+    // The squares behind the target at the line's stride (8, 1, 9, 7), not clipped to the board's
+    // edge: one periodic constant per stride, without the target's own bit, shifted once to end
+    // (toward lower squares) or start (toward higher ones) beside the target.  The ray came
+    // through empty squares, so the nearest occupied square at that stride is the origin, and a
+    // square where the stride wraps over an edge lies beyond it.
+    const bool file = d < 2, row = d < 4, dg = d == 5 || d == 6;
+    const u64 pl = file ? 0x0080808080808080ull : row ? 0x7FFFFFFFFFFFFFFFull : dg ? 0x0040201008040201ull : 0x0102040810204081ull;
+    const u64 ph = file ? 0x0101010101010100ull : row ? 0xFFFFFFFFFFFFFFFEull : dg ? 0x8040201008040200ull : 0x8102040810204080ull;
+    const u64 x = g.occ & (up ? pl >> (63 - to) : ph << to);
+    const int sl = x ? (up ? msb(x) : ctz(x)) : 0;
     const bool slider = j >= SW_ORTH && j < SW_K;
     return slider ? sl : to + off;
 }
@@ -1453,8 +1459,12 @@ GC_HD u64 byte_prefix(u64 w) {  // inclusive prefix sums of the 8 bytes (no byte
 // chains (it is the paired step's tail): the word from three independent compares against the
 // running word totals; the byte as 8 - the number of byte prefixes > k, counted by a borrow-free
 // compare of the bytes spread over 16-bit lanes.
-GC_HD int sw_locate(const u64* cw, int& k) {
-    const u64 p0 = byte_prefix(cw[0]), p1 = byte_prefix(cw[1]), p2 = byte_prefix(cw[2]), p3 = byte_prefix(cw[3]);
+// (sw_locate_pre: from the words' byte prefixes.  byte_prefix is a multiply by 0x0101...01, so
+// the prefixes of words whose sets several makers fill add up: byte_prefix(a | b) =
+// byte_prefix(a) + byte_prefix(b) for disjoint bytes, exact per byte while no sum reaches 256 --
+// the fused ply's makers each hand over the prefixes of their own counts)
+GC_HD int sw_locate_pre(const u64* pw, int& k) {
+    const u64 p0 = pw[0], p1 = pw[1], p2 = pw[2], p3 = pw[3];
     const int c1 = (int)(p0 >> 56), c2 = c1 + (int)(p1 >> 56), c3 = c2 + (int)(p2 >> 56);
     const int w = (k >= c1) + (k >= c2) + (k >= c3);
     const u64 p = w == 0 ? p0 : w == 1 ? p1 : w == 2 ? p2 : p3;
@@ -1464,6 +1474,10 @@ GC_HD int sw_locate(const u64* cw, int& k) {
     const int b = 8 - above;  // bytes with prefix <= k: the set is the next one
     k -= b ? (int)((p >> (8 * b - 8)) & 0xFF) : 0;
     return 8 * w + b;
+}
+GC_HD int sw_locate(const u64* cw, int& k) {
+    const u64 pw[4] = {byte_prefix(cw[0]), byte_prefix(cw[1]), byte_prefix(cw[2]), byte_prefix(cw[3])};
+    return sw_locate_pre(pw, k);
 }
 GC_HD int sw_finish(const Gen& g, int j, u64 tj, int k) {
     const int to = kth_set_bit(tj, k);
@@ -1670,11 +1684,14 @@ GC_HD int apply_move(Pos& s, bool white_player, int action, int* reward, bool* i
 // move revokes both white rights, a white rook leaving column 0 / 7 revokes one (Q5).
 // (occ0, kw, rw: occ_of(s), s.k & s.w, s.r & s.w of the position before the move -- the fused
 // ply has them ready before it learns the action)
+// (CASTLE false: for a caller that knows the action is no castle -- the fused ply tests its whole
+// wave -- the castle terms are the constants they reduce to and fold away)
+template <bool CASTLE = true>
 GC_HD void apply_legal_with(Pos& s, bool white, int action, int* reward, bool* irrev, u64 occ0, u64 kw, u64 rw) {
     // castles (lib.rs:740-773) in the same branch-free form: the king's and rook's squares
     // (and the ones between) cleared, king and rook put on their targets in the colour of the
     // castle id; both rights of that colour revoked
-    const bool cs = action >= 4096;
+    const bool cs = CASTLE && action >= 4096;
     const bool cw = action == A_KSW || action == A_QSW, cks = action == A_KSW || action == A_KSB;
     const int base = cw ? 56 : 0;
     const u64 cclr = cks ? (0xFull << (base + 4)) : (0x1Full << base);
@@ -1709,8 +1726,9 @@ struct ApplyMasks {
     u64 fm, tm, clr;     // from / to (0 for a castle), the squares kept
     u64 ck, cr;          // a castle's king and rook targets
 };
+template <bool CASTLE = true>
 GC_HD ApplyMasks apply_masks(int action) {
-    const bool cs = action >= 4096;
+    const bool cs = CASTLE && action >= 4096;
     const bool cw = action == A_KSW || action == A_QSW, cks = action == A_KSW || action == A_KSB;
     const int base = cw ? 56 : 0;
     const u64 cclr = cks ? (0xFull << (base + 4)) : (0x1Full << base);
@@ -1720,8 +1738,9 @@ GC_HD ApplyMasks apply_masks(int action) {
 }
 #define GC_MV(X) s.X = (s.X & m.clr) | ((s.X & m.fm) ? m.tm : 0ull)
 // k, r, w and meta (kw, rw: s.k & s.w, s.r & s.w before the move)
+template <bool CASTLE = true>
 GC_HD void apply_legal_krw(Pos& s, int action, u64 kw, u64 rw) {
-    const ApplyMasks m = apply_masks(action);
+    const ApplyMasks m = apply_masks<CASTLE>(action);
     const int f = (action >> 6) & 63;
     const bool wk = (kw & m.fm) != 0, wr = (rw & m.fm) != 0;
     GC_MV(k); GC_MV(r); GC_MV(w);
@@ -1735,8 +1754,9 @@ GC_HD void apply_legal_krw(Pos& s, int action, u64 kw, u64 rw) {
 }
 // q, b, n, p, the captured value and the irreversible flag (occ0: occ_of(s) before the move;
 // reads s.r for the value)
+template <bool CASTLE = true>
 GC_HD void apply_legal_qbnp(Pos& s, int action, int* reward, bool* irrev, u64 occ0) {
-    const ApplyMasks m = apply_masks(action);
+    const ApplyMasks m = apply_masks<CASTLE>(action);
     const int t = action & 63;
     const int v = 10 * (int)((s.q >> t) & 1) + 5 * (int)((s.r >> t) & 1) + 3 * (int)(((s.b | s.n) >> t) & 1) +
                   (int)((s.p >> t) & 1);

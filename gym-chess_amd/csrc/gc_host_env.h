@@ -1173,30 +1173,46 @@ extern "C" int gc_env_window_sum(gc_env* e, uint64_t* sum) {
 // one fused launch of n_plies (reference rules, opponent "none"), then 4 s_memrealtime stamps:
 // wave start, entry loads done, first ply done, last ply done.  run (or NULL; the quad rollout):
 // per wave, the plies in which the commit loaded a slot beyond the home slot and the cycles of
-// their phase 2 (Q1's waves; 0 for the other roles)
-extern "C" int gc_debug_pstamps(gc_env* e, int n_plies, uint64_t* out /* waves * 12 */, uint64_t* run /* waves * 2 */) {
+// their phase 2 (Q1's waves; 0 for the other roles).  last (or NULL; one quad per workgroup): per
+// wave and barrier A, B, C, D, the plies in which the wave arrived last, in PST_BINS bins of
+// PST_BIN_CYCLES of its margin over the next to last, then the margins' sum
+extern "C" int gc_debug_pstamps2(gc_env* e, int n_plies, uint64_t* out /* waves * 12 */, uint64_t* run /* waves * 2 */,
+                                 uint32_t* last /* waves * 4 * (PST_BINS + 1) */) {
     Temps tmps;
     unsigned long long *d = nullptr, *dr = nullptr;
+    unsigned* dl = nullptr;
     // waves of the fused launch: pairs (2 per 64 boards) or quads (4 per 64 boards)
     const LaunchGeom g = use_quad(e) ? roll_geom(board_blocks(e), roll_quads_wg(n_plies)) : pair_geom(board_blocks(e));
     const size_t waves = (size_t)g.grid.x * (g.block.x / 64);
+    const size_t nlast = waves * 4 * (PST_BINS + 1);
     if (tmps.alloc(&d, waves * 12)) return -1;
     HIPCHK(hipMemsetAsync(d, 0, waves * 96, e->stream));
     if (run) {
         if (tmps.alloc(&dr, waves * 2)) return -1;
         HIPCHK(hipMemsetAsync(dr, 0, waves * 16, e->stream));
     }
+    if (last) {
+        if (tmps.alloc(&dl, nlast)) return -1;
+        HIPCHK(hipMemsetAsync(dl, 0, nlast * 4, e->stream));
+    }
     HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &d, sizeof(d)));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_run_out), &dr, sizeof(dr)));
+    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_last_out), &dl, sizeof(dl)));
     if (issue_rollout(e, n_plies, nullptr, false)) return -1;
     HIPCHK(hipMemcpyAsync(out, d, waves * 96, hipMemcpyDeviceToHost, e->stream));
     if (run) HIPCHK(hipMemcpyAsync(run, dr, waves * 16, hipMemcpyDeviceToHost, e->stream));
+    if (last) HIPCHK(hipMemcpyAsync(last, dl, nlast * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     unsigned long long* z = nullptr;
+    unsigned* zl = nullptr;
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_out), &z, sizeof(z)));
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_run_out), &z, sizeof(z)));
+    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_pst_last_out), &zl, sizeof(zl)));
     return 0;
+}
+extern "C" int gc_debug_pstamps(gc_env* e, int n_plies, uint64_t* out, uint64_t* run) {
+    return gc_debug_pstamps2(e, n_plies, out, run, nullptr);
 }
 #endif
 

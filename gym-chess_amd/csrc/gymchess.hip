@@ -85,9 +85,51 @@ __device__ __forceinline__ void gc_pst_mark_run(int k, bool loaded) {
     __builtin_amdgcn_sched_barrier(0);
 }
 #define PST_LOADED(x) do { if (x) pst_loaded = true; } while (0)
+// the quad rollout, one quad per workgroup: which role arrives last at each of the ply's four
+// barriers (A, B, C, D) and by how much.  A wave leaves its arrival stamp (the segment stamp just
+// taken) before the barrier; after it each wave reads the four and the last one counts itself, in
+// bins of PST_BIN_CYCLES of its margin over the next to last (the last bin: all above), and adds
+// the margin up.  A slot is written again three barriers later, which every reader has to reach
+// first.
+#define PST_BINS 16
+#define PST_BIN_CYCLES 128
+__shared__ unsigned long long gc_pst_arr[4][4];      // [barrier][wave]
+__shared__ unsigned gc_pst_last[4][4][PST_BINS + 1];  // [wave][barrier][bin .. , the margins' sum]
+__device__ unsigned* g_pst_last_out;
+__device__ __forceinline__ void gc_pst_arrive(int b) {
+    __builtin_amdgcn_sched_barrier(0);
+    if ((threadIdx.x & 63) == 0) gc_pst_arr[b][(threadIdx.x >> 6) & 3] = gc_pst[threadIdx.x >> 6][8];
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void gc_pst_count_last(int b) {
+    __builtin_amdgcn_sched_barrier(0);
+    if ((threadIdx.x & 63) == 0) {
+        const int w = (threadIdx.x >> 6) & 3;
+        const unsigned long long mine = gc_pst_arr[b][w];
+        unsigned long long next = 0;  // the latest of the others
+        bool last = true;
+        for (int o = 0; o < 4; o++) {
+            if (o == w) continue;
+            const unsigned long long t = gc_pst_arr[b][o];
+            last = last && (t < mine || (t == mine && o > w));
+            next = t > next ? t : next;
+        }
+        if (last) {
+            const unsigned long long m = mine - next;
+            const unsigned bin = (unsigned)(m / PST_BIN_CYCLES);
+            gc_pst_last[w][b][bin < PST_BINS - 1 ? bin : PST_BINS - 1] += 1u;
+            gc_pst_last[w][b][PST_BINS] += (unsigned)m;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+#define PST_ARRIVE(b) gc_pst_arrive(b)
+#define PST_LAST(b) gc_pst_count_last(b)
 #else
 #define PST(k)
 #define PST_LOADED(x)
+#define PST_ARRIVE(b) ((void)0)
+#define PST_LAST(b) ((void)0)
 #endif
 #include "gc_core.h"
 #include "gc_env.h"
@@ -1517,12 +1559,13 @@ __device__ __forceinline__ Pos pair_settle(const PairHalf& H, bool white) {
 // The self-play pick from the move sets in LDS (pair_half with SW): the set holding rank k by
 // the byte counts (gc_core.h sw_locate), then that one set from LDS; more moves than byte sums
 // hold (never in play) take a rolled scan over LDS.  k < tot.
-template <class LdsT>
+// (PRE: cw holds the count words' byte prefixes, sw_locate_pre)
+template <bool PRE = false, class LdsT>
 __device__ __forceinline__ int sw_pick_lds(const LdsT& L, int l, const Gen& g, const u64* cw, int tot, int k) {
     const int normal = tot - popc(g.castles);
     int r = k, j;
     if (tot < 256) {
-        j = sw_locate(cw, r);
+        j = PRE ? sw_locate_pre(cw, r) : sw_locate(cw, r);
     } else {
 #pragma unroll 1
         for (j = 0; j < SW_SETS - 1; j++) {
@@ -2148,8 +2191,10 @@ struct QuadLds {
     u32 f0[QUAD_BOARDS];             // Q0 -> Q1: the side to move is in check
     u64 enemy[3][QUAD_BOARDS];       // Q2 / Q3 -> Q0, Q2: the enemy map's leaper + orthogonal ([1]), diagonal ([2]) parts
     u32 f1[QUAD_BOARDS];             // Q1 -> Q0: the mover is in check after its move
-    u64 cwx[2][4][QUAD_BOARDS];      // Q2 ([0]) / Q3 ([1]) -> Q2: their sets' byte counts (all four words)
-    u64 cw0[2][QUAD_BOARDS];         // Q0 -> Q2: its sets' byte counts (words 0, 1: pawns, knights)
+    // the sets' byte counts (gc_core.h sw_pack: set i in byte i % 8 of word i / 8) reach Q2 as
+    // byte prefixes (byte_prefix) of the words a maker owns; prefixes of disjoint bytes add
+    u64 cw3[QUAD_BOARDS];            // Q3 -> Q2: word 2 (the bishop / queen sets)
+    u64 cw0[2][QUAD_BOARDS];         // Q0 -> Q2: words 0, 1 (pawns, knights)
     u32 part[4][QUAD_BOARDS];        // partial move totals (Q0's holds the castles)
     u32 rep[QUAD_BOARDS];            // Q1 -> Q0: 3-fold count | window length << 8
     u32 x0[QUAD_BOARDS];             // Q3 (two quads per workgroup: Q1) -> Q2: the Philox word of the next draw
@@ -2302,20 +2347,39 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     bool irrev = false;
     Pos ns;
     // ---- phase 0
+    // A castle is played on one wave-ply in fifty (0.03 % of board-plies), so its terms of the
+    // apply -- the cleared squares, the king's and rook's targets, the selects on them -- are made
+    // only where a lane of the wave plays one
+    const bool cas = R < 2 && __any(mv && a >= 4096);
     if (R == 0 && S0) {  // the apply's king / rook / colour half
         ns = s;
         ns.meta = q0.meta0;  // State::new's rights
-        if (mv) apply_legal_krw(ns, a, q0.kw, q0.rw);
+        if (!mv) {
+        } else if (cas) {
+            apply_legal_krw(ns, a, q0.kw, q0.rw);
+        } else {
+            apply_legal_krw<false>(ns, a, q0.kw, q0.rw);
+        }
         L.ns[0][l] = ns.k; L.ns[2][l] = ns.r; L.ns[6][l] = ns.w;
         L.nmeta[l] = ns.meta;
     } else if (R == 1 && S0) {  // the other four boards, the capture's value, the irreversible flag
         ns = s;
-        if (mv) apply_legal_qbnp(ns, a, &mr, &irrev, q0.occ);
+        if (!mv) {
+        } else if (cas) {
+            apply_legal_qbnp(ns, a, &mr, &irrev, q0.occ);
+        } else {
+            apply_legal_qbnp<false>(ns, a, &mr, &irrev, q0.occ);
+        }
         L.ns[1][l] = ns.q; L.ns[3][l] = ns.b; L.ns[4][l] = ns.n; L.ns[5][l] = ns.p;
     } else if (R == 0) {
         ns = s;
         ns.meta = q0.meta0;  // State::new's rights
-        if (mv) apply_legal_with(ns, white, a, &mr, &irrev, q0.occ, q0.kw, q0.rw);
+        if (!mv) {
+        } else if (cas) {
+            apply_legal_with(ns, white, a, &mr, &irrev, q0.occ, q0.kw, q0.rw);
+        } else {
+            apply_legal_with<false>(ns, white, a, &mr, &irrev, q0.occ, q0.kw, q0.rw);
+        }
         L.ns[0][l] = ns.k; L.ns[1][l] = ns.q; L.ns[2][l] = ns.r; L.ns[3][l] = ns.b;
         L.ns[4][l] = ns.n; L.ns[5][l] = ns.p; L.ns[6][l] = ns.w;
         L.nmeta[l] = ns.meta;
@@ -2323,7 +2387,9 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         L.irrev[l] = irrev ? 1u : 0u;
     }
     PST(0);
+    if (S0) PST_ARRIVE(0);  // (GC_PSTAMPS, one quad per workgroup: who arrives last, per barrier)
     if (R != 1 || S0) pair_barrier();
+    if (S0) PST_LAST(0);
     PST(1);
     // ---- phase 1
     Gen g;
@@ -2377,7 +2443,9 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         L.enemy[2][l] = g.ks >= 0 ? side_attacks_diag(ns, !g.white, dc) : 0ull;
     }
     PST(2);
+    if (S0) PST_ARRIVE(1);
     pair_barrier();
+    if (S0) PST_LAST(1);
     PST(3);
     // ---- phase 2
 #define QUAD_ENEMY(l) (L.enemy[1][l] | L.enemy[2][l])
@@ -2410,8 +2478,8 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
             Q.put_all<SW_N, SW_ORTH>(T + SW_N);
             Q.part += popc(g.castles);
         }
-        L.cw0[0][l] = Q.cw[0];
-        L.cw0[1][l] = Q.cw[1];
+        L.cw0[0][l] = byte_prefix(Q.cw[0]);
+        L.cw0[1][l] = byte_prefix(Q.cw[1]);
         L.castles[l] = g.castles;
     } else if (R == 1) {
         if (mv && !both) {
@@ -2455,15 +2523,15 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         sw_kings(ns, g, T);
         Q.put_all<SW_K, SW_SETS>(T + SW_K);
         L.part[2][l] = (u32)Q.part;
+        // (word 0 holds none of Q2's sets; its own words' prefixes stay in registers across barrier C)
 #pragma unroll
-        for (int k = 0; k < 4; k++) L.cwx[0][k][l] = Q.cw[k];
+        for (int k = 1; k < 4; k++) Q.cw[k] = byte_prefix(Q.cw[k]);
     } else {
         u64 T[SW_SETS];
         sw_diag(ns, g, dc, T);
         Q.put_all<SW_DIAG, SW_K>(T + SW_DIAG);
         L.part[3][l] = (u32)Q.part;
-#pragma unroll
-        for (int k = 0; k < 4; k++) L.cwx[1][k][l] = Q.cw[k];
+        L.cw3[l] = byte_prefix(Q.cw[2]);  // its four sets are bytes of word 2
     }
     if (R == 0) L.part[0][l] = (u32)Q.part;
 #ifdef GC_PSTAMPS
@@ -2471,7 +2539,9 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     else
 #endif
     PST(4);
+    if (S0) PST_ARRIVE(2);
     pair_barrier();
+    if (S0) PST_LAST(2);
     PST(5);
     // ---- phase 3: the outcome (Q0 and Q1, identical arithmetic); Q2 picks the next action
     // from the move sets (Q0 takes it, or the reset table's, at the start of the next ply)
@@ -2480,14 +2550,12 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     if (R == 2) QSETPRIO(2, up);
     if (R == 2) {  // (on Q3, whose SIMDs Q1 shares: 12.77-12.98 vs 13.30-13.42e9)
         const int total = (int)L.part[0][l] + Q.part + (int)L.part[3][l];
-        u64 cw[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) cw[k] = Q.cw[k] | L.cwx[1][k][l];
-        cw[0] |= L.cw0[0][l];
-        cw[1] |= L.cw0[1][l];
+        // the words' byte prefixes, summed where two makers meet (word 1: Q0's knights and the
+        // rook / queen sets here; word 2: Q3's sets and the king's)
+        const u64 cw[4] = {L.cw0[0][l], Q.cw[1] + L.cw0[1][l], Q.cw[2] + L.cw3[l], Q.cw[3]};
         g.castles = L.castles[l];
         // (a board whose generation is not due reads stale sets here: its pick is not taken)
-        L.pick[l] = total > 0 ? (u32)sw_pick_lds(L, l, g, cw, total, (int)scale_rank(L.x0[l], (u32)total)) : (u32)A_NONE;
+        L.pick[l] = total > 0 ? (u32)sw_pick_lds<true>(L, l, g, cw, total, (int)scale_rank(L.x0[l], (u32)total)) : (u32)A_NONE;
     }
     if constexpr (CARRY) {
         const int total = gen ? (R == 0 ? Q.part : (int)L.part[0][l]) + (int)L.part[2][l] + (int)L.part[3][l] : 0;
@@ -2568,7 +2636,9 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
         quad_ahead(C, i, d, ah);
     }
     PST(6);
+    if (S0) PST_ARRIVE(3);
     pair_barrier();  // Q2's pick to Q0; LDS free for the next ply
+    if (S0) PST_LAST(3);
     return o;
 }
 
@@ -2664,6 +2734,9 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
     if (l == 0) {
         for (int k = 0; k < 8; k++) gc_pst[threadIdx.x >> 6][k] = 0;
         gc_pst_run[threadIdx.x >> 6][0] = gc_pst_run[threadIdx.x >> 6][1] = 0;
+        if (S0)
+            for (int b = 0; b < 4; b++)
+                for (int k = 0; k <= PST_BINS; k++) gc_pst_last[threadIdx.x >> 6][b][k] = 0;
         gc_pst[threadIdx.x >> 6][8] = __builtin_amdgcn_s_memtime();
     }
     const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
@@ -2719,6 +2792,10 @@ __device__ __forceinline__ void quad_run(uint8_t* __restrict__ slab, int nn, uin
             g_pst_run_out[w * 2] = gc_pst_run[threadIdx.x >> 6][0];
             g_pst_run_out[w * 2 + 1] = gc_pst_run[threadIdx.x >> 6][1];
         }
+        if (S0 && g_pst_last_out != nullptr)
+            for (int b = 0; b < 4; b++)
+                for (int k = 0; k <= PST_BINS; k++)
+                    g_pst_last_out[(w * 4 + b) * (PST_BINS + 1) + k] = gc_pst_last[threadIdx.x >> 6][b][k];
     }
 #endif
     if (!live || RR >= 2) return;

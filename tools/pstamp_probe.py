@@ -5,7 +5,9 @@ k_env_rollout2<false, 0> (phase work and barrier waits, s_memtime), summed over 
 phase 2 | wait C | phase 3 (outcome, pick / commit) | wait D (next action to W1).  The quad
 rollout's Q1 also reports phase 2 by whether a lane of the wave loaded a window slot beyond its
 home slot in that ply (rep_commit's in-loop load; -DGC_OCC_RUN=0 builds the form that loads
-every slot)."""
+every slot).  With one quad per workgroup (PST_QUAD=1 PST_WG=1) it also prints, per barrier A-D,
+which role arrived last in how many of the quad-plies and by how much: the mean margin over the
+next-to-last role and a histogram of it (gc_debug_pstamps2)."""
 import ctypes
 import os
 import sys
@@ -30,7 +32,13 @@ wg1 = os.environ.get("PST_WG") == "1"
 waves = ((n + 63) // 64) * 4 if quad and wg1 else ((n + 127) // 128) * (8 if quad else 4)
 out = np.zeros(waves * 12, dtype=np.uint64)
 run = np.zeros(waves * 2, dtype=np.uint64)  # the quad rollout's Q1: plies with an in-loop window load, their phase 2
-assert L.gc_debug_pstamps(h, plies, out.ctypes.data_as(P), run.ctypes.data_as(P)) == 0
+PST_BINS, PST_BIN_CYCLES = 16, 128  # gymchess.hip
+last = np.zeros(waves * 4 * (PST_BINS + 1), dtype=np.uint32)  # who arrived last at each barrier, by margin
+if quad and wg1 and hasattr(L, "gc_debug_pstamps2"):
+    L.gc_debug_pstamps2.argtypes = [P, ctypes.c_int, P, P, P]
+    assert L.gc_debug_pstamps2(h, plies, out.ctypes.data_as(P), run.ctypes.data_as(P), last.ctypes.data_as(P)) == 0
+else:
+    assert L.gc_debug_pstamps(h, plies, out.ctypes.data_as(P), run.ctypes.data_as(P)) == 0
 raw = out.reshape(-1, 12)
 st = raw[:, :8].astype(np.float64) / plies
 where = (raw[:, 8] >> np.uint64(44)).astype(np.int64)  # placement: cu | sh | se | simd | xcc
@@ -69,6 +77,17 @@ for r in roles:
         without = len(rn) * plies - with_load
         print(f"   phase 2, plies with an in-loop window load: {with_load / (len(rn) * plies):.4f} of wave-plies, "
               f"{rn[:, 1].sum() / max(with_load, 1):.0f} cycles; without: {(p2 - rn[:, 1].sum()) / max(without, 1):.0f} cycles")
+if quad and wg1 and last.any():  # the last arrival per barrier: the role, how often, by how much
+    la = last.reshape(-1, 4, PST_BINS + 1).astype(np.float64)
+    print(f"last arrival per barrier (share of quad-plies, mean margin over the next to last in cycles; "
+          f"histogram of the margin in bins of {PST_BIN_CYCLES} cycles, the last bin open, % of the barrier's quad-plies)")
+    for b, bname in enumerate("ABCD"):
+        allq = la[:, b, :PST_BINS].sum()
+        for r in roles:
+            hb = la[role == r, b, :PST_BINS].sum(axis=0)
+            cnt = hb.sum()
+            print(f"   barrier {bname} Q{r}: {cnt / max(allq, 1):6.1%}  margin {la[role == r, b, PST_BINS].sum() / max(cnt, 1):6.0f}  | "
+                  + " ".join(f"{100 * v / max(allq, 1):4.1f}" for v in hb))
 if quad:  # where the slow waves run (k_env_rollout4): wave end and per-ply time by XCD and by CU
     xcc = where >> 9
     cu_key = where & 0x7F | (xcc << 7)
