@@ -18,13 +18,15 @@ rules="fide" plays FIDE chess (gym-chess_amd/csrc/gc_fide.h, SURVEY.md §8f row 
 reference env's rewards and bookkeeping; an action promotes to a queen.
 """
 import ctypes
-import os
 import weakref
 
 import numpy as np
 
 from . import _lib
+from . import buffers as B
 from . import codec as C
+from .buffers import (DeviceIO, PlanesBuffer, PriorsBuffer, RowsBuffer, TraceBuffer, _DeviceArrays,  # noqa: F401
+                      _GumbelPolicy, _Staging, c_pointers, fetch_arrays, planes_format, upload, upload_indices)
 
 REASONS = {0: "none", 1: "mate", 2: "repetition", 3: "move_cap", 4: "no_moves", 5: "both_kings_checked",
            6: "invalid_action", 7: "already_done", 8: "mated_by_opponent", 9: "opponent_no_move",
@@ -38,6 +40,10 @@ class BatchedChessEnv:
         self.num_boards = int(num_boards)
         self.device = int(device)
         self.seed = int(seed)
+        # the uploaded lists of policy_priors (int32 boards), step_boards / encode_planes_rows (int32
+        # boards + uint16 actions) and clone_boards (2 x int32 indices); step_boards' own rows buffer
+        self._staging = {"priors": _Staging(self, 4), "rows": _Staging(self, 6), "clone": _Staging(self, 8)}
+        self._rows_out = None
         ib = None
         if initial_board is not None:
             ib = C.board_to_array(initial_board)
@@ -68,9 +74,12 @@ class BatchedChessEnv:
                 if st is not None:
                     st.close()
             self._stores = []
-            self._clone_free()
-            self._priors_free()
-            self._rows_free()
+            for st in self._staging.values():
+                st.close()
+            if self._rows_out is not None:
+                self.synchronize()
+                self._rows_out.close()
+                self._rows_out = None
             self._L.gc_env_destroy(self._h)
             self._h = None
 
@@ -313,7 +322,7 @@ class BatchedChessEnv:
                                                p.get("obs"), p.get("count"), p.get("pick"), int(bool(autoreset)),
                                                io.mask_stride))
 
-    POLICY_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+    POLICY_DTYPES = B.POLICY_DTYPES
 
     def sample_policy(self, io, logits, dtype="float32", row_stride=4100, temperature=1.0, seed=None, draw=0,
                       greedy=False, action=None, relative=False):
@@ -379,14 +388,7 @@ class BatchedChessEnv:
                 raise ValueError("a device pointer needs rows")
             pb, m = boards or None, int(rows)
         else:
-            b = np.ascontiguousarray(boards, dtype=np.int64).reshape(-1)
-            if rows is not None and int(rows) != b.size:
-                raise ValueError(f"rows {rows} != the board array's length {b.size}")
-            b = np.clip(b, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
-            pb, m = None, int(b.size)
-            if m:
-                pb = self._priors_staging(m)
-                _lib.check(self._L.gc_env_copy(self._h, pb, _lib.ptr(b), ctypes.c_uint64(b.nbytes), 1))
+            pb, m = upload_indices(self._staging["priors"], boards, rows)
         if m > out.rows:
             raise ValueError(f"{m} rows, the priors buffer holds {out.rows}")
         p = out.ptr
@@ -395,25 +397,9 @@ class BatchedChessEnv:
                                                 2 if relative else 0, out.cap, p["actions"], p["priors"], p["count"],
                                                 p.get("logit_index")))
 
-    def _priors_staging(self, m):
-        """device int32[cap] for policy_priors' uploaded board indices, grown by doubling"""
-        if m > getattr(self, "_priors_cap", 0):
-            self._priors_free()  # (gc_device_free waits for the device: no launch still reads it)
-            cap = max(256, 1 << (m - 1).bit_length())
-            v = ctypes.c_void_p()
-            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(4 * cap), ctypes.byref(v)))
-            self._priors_buf, self._priors_cap = v.value, cap
-        return self._priors_buf
-
-    def _priors_free(self):
-        if getattr(self, "_priors_buf", None):
-            self.synchronize()
-            self._L.gc_device_free(self.device, ctypes.c_void_p(self._priors_buf))
-        self._priors_buf, self._priors_cap = None, 0
-
     # ------------------------------------------------------------------ network input planes
-    PLANES = 24
-    PLANES_LAYOUTS = {"nchw": 0, "nhwc": 2}
+    PLANES = B.PLANES
+    PLANES_LAYOUTS = B.PLANES_LAYOUTS
 
     def planes_buffer(self, dtype="float16", layout="nchw", board_stride=None, rows=None):
         """device memory for encode_planes: [N][board_stride] elements of `dtype` (None = 24 * 64);
@@ -430,17 +416,9 @@ class BatchedChessEnv:
         [N,8,8,24].  perspective: the side-to-move view (the side to move comes first, and boards
         with BLACK to move are mirrored top to bottom); sample_policy(relative=True) reads a
         policy head's logits in the same view."""
-        buf = out if isinstance(out, PlanesBuffer) else None
-        dtype = dtype if dtype is not None else (buf.dtype if buf else "float16")
-        layout = layout if layout is not None else (buf.layout if buf else "nchw")
-        if board_stride is None:
-            board_stride = buf.board_stride if buf else 0
-        if dtype not in self.POLICY_DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
-        if layout not in self.PLANES_LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
+        buf, dtype, layout, board_stride = planes_format(out, dtype, layout, board_stride)
         _lib.check(self._L.gc_env_encode_planes(self._h, buf.ptr if buf else int(out), self.POLICY_DTYPES[dtype],
-                                                int(board_stride), self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
+                                                board_stride, self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
 
     def encode_planes_rows(self, out, boards, rows=None, dtype=None, layout=None, perspective=False, row_stride=None):
         """encode_planes of the listed boards only, row-compact (gc_env_encode_planes_rows): row j
@@ -451,20 +429,12 @@ class BatchedChessEnv:
         synchronous copy as clone_boards') or a device pointer (int) to int32[rows], with rows.
         Duplicates are fine; an index outside [0, N) gives an all-zero row.  Everything else as
         encode_planes; any env, asynchronous on the env's stream."""
-        buf = out if isinstance(out, PlanesBuffer) else None
-        dtype = dtype if dtype is not None else (buf.dtype if buf else "float16")
-        layout = layout if layout is not None else (buf.layout if buf else "nchw")
-        if row_stride is None:
-            row_stride = buf.board_stride if buf else 0
-        if dtype not in self.POLICY_DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(self.POLICY_DTYPES)}, got {dtype!r}")
-        if layout not in self.PLANES_LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(self.PLANES_LAYOUTS)}, got {layout!r}")
+        buf, dtype, layout, row_stride = planes_format(out, dtype, layout, row_stride)
         pb, m = self._rows_indices(boards, rows)
         if buf and m > buf.rows:
             raise ValueError(f"{m} rows, the planes buffer holds {buf.rows}")
         _lib.check(self._L.gc_env_encode_planes_rows(self._h, pb, m, buf.ptr if buf else int(out),
-                                                     self.POLICY_DTYPES[dtype], int(row_stride),
+                                                     self.POLICY_DTYPES[dtype], row_stride,
                                                      self.PLANES_LAYOUTS[layout] | int(bool(perspective))))
 
     # ------------------------------------------------------------------ indexed step (search)
@@ -504,15 +474,15 @@ class BatchedChessEnv:
             a = a.astype(np.uint16)
             pa = None
             if m:
-                pa = self._rows_staging(m) + 4 * self._rows_cap
-                _lib.check(self._L.gc_env_copy(self._h, pa, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+                st = self._staging["rows"]  # int32 boards[cap], then uint16 actions[cap]
+                pa = st.reserve(m) + 4 * st.cap
+                upload(self, pa, a)
         if out is None:
-            if m > getattr(self, "_rows_out_rows", -1):
-                if getattr(self, "_rows_out", None):
+            if self._rows_out is None or m > self._rows_out.rows:
+                if self._rows_out is not None:
                     self.synchronize()
                     self._rows_out.close()
                 self._rows_out = RowsBuffer(self, max(256, 1 << max(m - 1, 0).bit_length()))
-                self._rows_out_rows = self._rows_out.rows
             out = self._rows_out
         elif not isinstance(out, RowsBuffer):
             raise TypeError("out must be a rows_buffer()")
@@ -531,35 +501,7 @@ class BatchedChessEnv:
             if rows is None:
                 raise ValueError("a device pointer needs rows")
             return boards or None, int(rows)
-        b = np.ascontiguousarray(boards, dtype=np.int64).reshape(-1)
-        if rows is not None and int(rows) != b.size:
-            raise ValueError(f"rows {rows} != the board array's length {b.size}")
-        b = np.clip(b, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
-        if not b.size:
-            return None, 0
-        pb = self._rows_staging(int(b.size))
-        _lib.check(self._L.gc_env_copy(self._h, pb, _lib.ptr(b), ctypes.c_uint64(b.nbytes), 1))
-        return pb, int(b.size)
-
-    def _rows_staging(self, m):
-        """device int32[cap] boards + uint16[cap] actions for the uploaded lists, grown by doubling"""
-        if m > getattr(self, "_rows_cap", 0):
-            self._rows_free(out=False)  # (gc_device_free waits for the device: no launch still reads it)
-            cap = max(256, 1 << (m - 1).bit_length())
-            v = ctypes.c_void_p()
-            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(6 * cap), ctypes.byref(v)))
-            self._rows_buf, self._rows_cap = v.value, cap
-        return self._rows_buf
-
-    def _rows_free(self, out=True):
-        if getattr(self, "_rows_buf", None):
-            self.synchronize()
-            self._L.gc_device_free(self.device, ctypes.c_void_p(self._rows_buf))
-        self._rows_buf, self._rows_cap = None, 0
-        if out and getattr(self, "_rows_out", None):
-            self.synchronize()
-            self._rows_out.close()
-            self._rows_out, self._rows_out_rows = None, -1
+        return upload_indices(self._staging["rows"], boards, rows)
 
     # ------------------------------------------------------------------ board clones (search)
     def clone_boards(self, src, src_idx, dst_idx, count=None):
@@ -582,36 +524,13 @@ class BatchedChessEnv:
                 raise ValueError("device pointers need count")
             m, ps, pd = int(count), src_idx or None, dst_idx or None
         else:
-            s = np.ascontiguousarray(src_idx, dtype=np.int32).reshape(-1)
-            d = np.ascontiguousarray(dst_idx, dtype=np.int32).reshape(-1)
-            if s.size != d.size:
-                raise ValueError(f"src_idx holds {s.size} indices, dst_idx {d.size}")
-            if count is not None and int(count) != s.size:
-                raise ValueError(f"count {count} != the arrays' length {s.size}")
-            m = int(s.size)
-            ps = pd = None
-            if m:
-                ps = self._clone_staging(m)
-                pd = ps + 4 * self._clone_cap
-                for p, a in ((ps, s), (pd, d)):  # on the env's stream: after the previous clone read them
-                    _lib.check(self._L.gc_env_copy(self._h, p, _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
+            st = self._staging["clone"]  # int32[2][cap]; on the env's stream: after the previous clone read them
+            (ps, m), (pd, md) = upload_indices(st, src_idx), upload_indices(st, dst_idx, part=1)
+            if m != md:  # (a longer dst_idx may have replaced the buffer ps points into: nothing is launched)
+                raise ValueError(f"src_idx holds {m} indices, dst_idx {md}")
+            if count is not None and int(count) != m:
+                raise ValueError(f"count {count} != the arrays' length {m}")
         _lib.check(self._L.gc_env_clone_boards(self._h, src._h, ps, pd, m))
-
-    def _clone_staging(self, m):
-        """device int32[2][cap] for clone_boards' uploaded indices, grown by doubling"""
-        if m > getattr(self, "_clone_cap", 0):
-            self._clone_free()  # (gc_device_free waits for the device: no clone still reads it)
-            cap = max(256, 1 << (m - 1).bit_length())
-            v = ctypes.c_void_p()
-            _lib.check(self._L.gc_device_alloc(self.device, ctypes.c_uint64(8 * cap), ctypes.byref(v)))
-            self._clone_buf, self._clone_cap = v.value, cap
-        return self._clone_buf
-
-    def _clone_free(self):
-        if getattr(self, "_clone_buf", None):
-            self.synchronize()
-            self._L.gc_device_free(self.device, ctypes.c_void_p(self._clone_buf))
-        self._clone_buf, self._clone_cap = None, 0
 
     def clone_errors(self):
         """pairs clone_boards skipped into this env since its creation (an index out of range);
@@ -673,232 +592,6 @@ class BatchedChessEnv:
     def load_from(self, path):
         with open(path, "rb") as f:
             self.load(f.read())
-
-
-class TraceBuffer:
-    """Device trace of rollout_device: one uint64 word per board per ply ([ply][board]):
-    action played (int16, -1 = the driver's no-move reset), reward (int16), done, reason."""
-
-    def __init__(self, env, plies):
-        self.env = env
-        self.plies = int(plies)
-        v = ctypes.c_void_p()
-        _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(8 * self.plies * env.num_boards),
-                                          ctypes.byref(v)))
-        self.ptr = v.value
-
-    def fetch(self, plies=None):
-        """host copy of the first `plies` plies as dict(action, reward, done, reason) [ply][board]"""
-        w = self.raw(plies)
-        return dict(action=(w & np.uint64(0xFFFF)).astype(np.uint16).view(np.int16),
-                    reward=((w >> np.uint64(16)) & np.uint64(0xFFFF)).astype(np.uint16).view(np.int16),
-                    done=((w >> np.uint64(32)) & np.uint64(0xFF)).astype(np.uint8),
-                    reason=((w >> np.uint64(40)) & np.uint64(0xFF)).astype(np.uint8))
-
-    def raw(self, plies=None):
-        """host copy of the first `plies` plies as the packed words, uint64 [ply][board]"""
-        k = self.plies if plies is None else int(plies)
-        w = np.zeros((k, self.env.num_boards), dtype=np.uint64)
-        if w.size:
-            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(w), self.ptr, ctypes.c_uint64(w.nbytes), 2))
-        return w
-
-    def close(self):
-        if self.ptr:
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(self.ptr))
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlanesBuffer:
-    """Device memory of encode_planes' output: [rows][board_stride] raw elements of `dtype`
-    (board_stride >= 24 * 64 elements, a multiple of 8; rows = N, or the row count of an
-    encode_planes_rows batch)."""
-
-    _RAW = {"float32": np.float32, "float16": np.uint16, "bfloat16": np.uint16}
-
-    def __init__(self, env, dtype="float16", layout="nchw", board_stride=None, rows=None):
-        if dtype not in self._RAW:
-            raise ValueError(f"dtype must be one of {sorted(self._RAW)}, got {dtype!r}")
-        if layout not in env.PLANES_LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(env.PLANES_LAYOUTS)}, got {layout!r}")
-        self.env, self.dtype, self.layout = env, dtype, layout
-        self.board_stride = int(env.PLANES * 64 if board_stride is None else board_stride)
-        if self.board_stride < env.PLANES * 64 or self.board_stride % 8:
-            raise ValueError(f"board_stride {self.board_stride}: at least {env.PLANES * 64}, a multiple of 8")
-        self.rows = env.num_boards if rows is None else int(rows)
-        if self.rows < 0:
-            raise ValueError(f"rows {rows} < 0")
-        self.nbytes = self.rows * self.board_stride * np.dtype(self._RAW[dtype]).itemsize
-        v = ctypes.c_void_p()
-        _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self.nbytes), ctypes.byref(v)))
-        self.ptr = v.value
-
-    def raw(self):
-        """host copy of the raw elements, [rows][board_stride] (float32, or uint16 bit patterns)"""
-        a = np.zeros((self.rows, self.board_stride), dtype=self._RAW[self.dtype])
-        if a.nbytes:
-            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr, ctypes.c_uint64(a.nbytes), 2))
-        return a
-
-    def fetch(self):
-        """host copy decoded to float32: [rows,24,8,8] ("nchw") or [rows,8,8,24] ("nhwc")"""
-        a = self.raw()[:, : self.env.PLANES * 64]
-        if self.dtype == "float16":
-            a = a.view(np.float16).astype(np.float32)
-        elif self.dtype == "bfloat16":
-            a = (a.astype(np.uint32) << np.uint32(16)).view(np.float32)
-        shape = (24, 8, 8) if self.layout == "nchw" else (8, 8, 24)
-        return np.ascontiguousarray(a).reshape((self.rows,) + shape)
-
-    def close(self):
-        if self.ptr:
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(self.ptr))
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RowsBuffer:
-    """Device memory of step_boards' row-compact outputs: reward int32[rows], done uint8[rows],
-    reason uint8[rows] and optionally count int32[rows], obs int8[rows][64] (ptr[...] are device
-    pointers; row j belongs to the j-th listed board of the call)."""
-
-    _SPEC = {"reward": (np.int32, ()), "done": (np.uint8, ()), "reason": (np.uint8, ()), "count": (np.int32, ()),
-             "obs": (np.int8, (64,))}
-
-    def __init__(self, env, rows, obs=True, count=True):
-        self.env, self.rows = env, int(rows)
-        if self.rows < 0:
-            raise ValueError(f"rows {rows} < 0")
-        self.ptr = {}
-        for k in ("reward", "done", "reason") + (("count",) if count else ()) + (("obs",) if obs else ()):
-            v = ctypes.c_void_p()
-            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self._shape(k)[1]), ctypes.byref(v)))
-            self.ptr[k] = v.value
-
-    def _shape(self, k):
-        dt, sh = self._SPEC[k]
-        shape = (self.rows,) + sh
-        return shape, int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
-
-    def fetch(self, *keys):
-        """host copies (waits for the env's stream): dict of [rows] / [rows][64] arrays"""
-        out = {}
-        for k in keys or self.ptr:
-            shape, nb = self._shape(k)
-            a = np.zeros(shape, dtype=self._SPEC[k][0])
-            if nb:
-                _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(nb), 2))
-            out[k] = a
-        return out
-
-    def close(self):
-        for v in self.ptr.values():
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
-        self.ptr = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PriorsBuffer:
-    """Device memory of policy_priors' output: actions uint16[rows][cap], priors float32[rows][cap],
-    count int32[rows] and optionally logit_index uint16[rows][cap] (ptr[...] are device pointers)."""
-
-    _SPEC = {"actions": np.uint16, "priors": np.float32, "count": np.int32, "logit_index": np.uint16}
-
-    def __init__(self, env, rows, cap=64, logit_index=False):
-        self.env, self.rows, self.cap = env, int(rows), int(cap)
-        if self.rows < 0:
-            raise ValueError(f"rows {rows} < 0")
-        if not 1 <= self.cap <= C.N_ACTIONS - 1:
-            raise ValueError(f"cap {cap}: between 1 and {C.N_ACTIONS - 1}")
-        self.ptr = {}
-        for k in ("actions", "priors", "count") + (("logit_index",) if logit_index else ()):
-            v = ctypes.c_void_p()
-            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(self._shape(k)[1]), ctypes.byref(v)))
-            self.ptr[k] = v.value
-
-    def _shape(self, k):
-        shape = (self.rows,) if k == "count" else (self.rows, self.cap)
-        return shape, int(np.prod(shape, dtype=np.int64)) * np.dtype(self._SPEC[k]).itemsize
-
-    def fetch(self, *keys):
-        """host copies (waits for the env's stream): dict of [rows][cap] / [rows] arrays"""
-        out = {}
-        for k in keys or self.ptr:
-            shape, nb = self._shape(k)
-            a = np.zeros(shape, dtype=self._SPEC[k])
-            if nb:
-                _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(nb), 2))
-            out[k] = a
-        return out
-
-    def close(self):
-        for v in self.ptr.values():
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
-        self.ptr = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _DeviceArrays:
-    """device arrays a SearchTree owns: ptr[...] device pointers, fetch() host copies"""
-
-    def __init__(self, env, spec):
-        self.env, self._spec, self.ptr = env, spec, {}
-        for k, (dt, shape) in spec.items():
-            v = ctypes.c_void_p()
-            nb = int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
-            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(nb), ctypes.byref(v)))
-            self.ptr[k] = v.value
-
-    def __getattr__(self, k):
-        ptr = self.__dict__.get("ptr", {})
-        if k in ptr:
-            return ptr[k]
-        raise AttributeError(k)
-
-    def fetch(self, *keys):
-        """host copies (waits for the env's stream)"""
-        out = {}
-        for k in keys or self.ptr:
-            dt, shape = self._spec[k]
-            a = np.zeros(shape, dtype=dt)
-            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
-            out[k] = a
-        return out
-
-    def close(self):
-        for v in self.ptr.values():
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
-        self.ptr = {}
-
-
-class _GumbelPolicy(_DeviceArrays):
-    """gumbel_policy()'s buffers: a root_policy()-like result whose training target is `target`
-    (the improved policy in units of 2^-20) where root_policy's is `visits`"""
-
-    @property
-    def gumbel(self):
-        return True
 
 
 class SearchTree:
@@ -974,9 +667,7 @@ class SearchTree:
         h = ctypes.c_void_p()
         _lib.check(self._L.gc_tree_create(env._h, self.games, self.nodes, self.cap, ctypes.byref(h)))
         self._h = h
-        addr = (ctypes.c_void_p * len(self.ARRAYS))()
-        _lib.check(self._L.gc_tree_pointers(self._h, addr, len(self.ARRAYS)))
-        self.ptr = {k: addr[i] for i, k in enumerate(self.ARRAYS)}
+        self.ptr = c_pointers(self._L.gc_tree_pointers, self._h, self.ARRAYS)
         G, C_ = self.games, self.cap
         self._sel = _DeviceArrays(env, {"parent": (np.int32, (G,)), "child": (np.int32, (G,)),
                                         "action": (np.uint16, (G,))})
@@ -999,9 +690,7 @@ class SearchTree:
         """turns the solver on (gc_tree_solver_enable: once, and only while nothing is pending and
         no batch scratch is reserved); its arrays join ptr[...] / fetch()"""
         _lib.check(self._L.gc_tree_solver_enable(self._h))
-        addr = (ctypes.c_void_p * len(self.SOLVER_ARRAYS))()
-        _lib.check(self._L.gc_tree_solver_pointers(self._h, addr, len(self.SOLVER_ARRAYS)))
-        self.ptr.update({k: addr[i] for i, k in enumerate(self.SOLVER_ARRAYS)})
+        self.ptr.update(c_pointers(self._L.gc_tree_solver_pointers, self._h, self.SOLVER_ARRAYS))
         if self._proof is None:
             G = self.games
             self._proof = _DeviceArrays(self.env, {"status": (np.uint8, (G,)), "plies": (np.uint16, (G,)),
@@ -1014,9 +703,7 @@ class SearchTree:
         reallocates and disarms); its arrays join ptr[...] / fetch()"""
         considered, sims = int(considered), int(sims)
         _lib.check(self._L.gc_tree_gumbel_enable(self._h, considered, sims, float(c_visit), float(c_scale)))
-        addr = (ctypes.c_void_p * len(self.GUMBEL_ARRAYS))()
-        _lib.check(self._L.gc_tree_gumbel_pointers(self._h, addr, len(self.GUMBEL_ARRAYS)))
-        self.ptr.update({k: addr[i] for i, k in enumerate(self.GUMBEL_ARRAYS)})
+        self.ptr.update(c_pointers(self._L.gc_tree_gumbel_pointers, self._h, self.GUMBEL_ARRAYS))
         if self._gpol is None:
             G, C_ = self.games, self.cap
             self._gpol = _GumbelPolicy(self.env, {"actions": (np.uint16, (G, C_)), "visits": (np.int32, (G, C_)),
@@ -1108,9 +795,7 @@ class SearchTree:
         nothing is pending); its arrays join ptr[...] / fetch()"""
         K = int(max_leaves)
         _lib.check(self._L.gc_tree_batch_reserve(self._h, K))
-        addr = (ctypes.c_void_p * len(self.BATCH_ARRAYS))()
-        _lib.check(self._L.gc_tree_batch_pointers(self._h, addr, len(self.BATCH_ARRAYS)))
-        self.ptr.update({k: addr[i] for i, k in enumerate(self.BATCH_ARRAYS)})
+        self.ptr.update(c_pointers(self._L.gc_tree_batch_pointers, self._h, self.BATCH_ARRAYS))
         if K != self.max_leaves:
             if self._bsel is not None:
                 self.env.synchronize()  # (no env call still reads the old buffers)
@@ -1192,42 +877,27 @@ class SearchTree:
             if self._moves is None:
                 self._moves = _DeviceArrays(self.env, {"moves": (np.uint16, (self.games,))})
             pm = self._moves.ptr["moves"]
-            _lib.check(self._L.gc_env_copy(self.env._h, pm, _lib.ptr(m), ctypes.c_uint64(m.nbytes), 1))
+            upload(self.env, pm, m)
         _lib.check(self._L.gc_tree_advance(self._h, pm, a, p, c, pc, int(value) if value else None,
                                            self._adv.ptr["kept"], self._adv.ptr["remap"]))
         return self._adv
 
     def fetch(self, *keys):
         """host copies of the tree's arrays (waits for the env's stream)"""
-        out = {}
-        for k in keys or self.ARRAYS:
-            a = np.zeros(self._shape(k), dtype=self._DTYPES.get(k, np.int32))
-            _lib.check(self._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
-            out[k] = a
-        return out
+        return fetch_arrays(self.env, self.ptr, keys or self.ARRAYS,
+                            lambda k: (self._DTYPES.get(k, np.int32), self._shape(k)))
 
     def device_bytes(self):
         return int(self._L.gc_tree_device_bytes(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.gc_tree_destroy(self._h)  # (waits for the device)
+            self._L.gc_tree_destroy(self._h)  # (waits for the device; frees the arrays of ptr[...])
             self._h = None
-            self._sel.close()
-            self._root.close()
-            self._adv.close()
-            if self._bsel is not None:
-                self._bsel.close()
-                self._bsel = None
-            if self._moves is not None:
-                self._moves.close()
-                self._moves = None
-            if self._proof is not None:
-                self._proof.close()
-                self._proof = None
-            if self._gpol is not None:
-                self._gpol.close()
-                self._gpol = None
+            for name in ("_sel", "_root", "_adv", "_bsel", "_moves", "_proof", "_gpol"):  # the Python side's own
+                if getattr(self, name) is not None:
+                    getattr(self, name).close()
+                    setattr(self, name, None)
             self.ptr = {}
 
     def __del__(self):
@@ -1279,14 +949,12 @@ class SampleStore:
         self._h = None
         self._batch = None  # sample()'s own output buffers and their key
         self._batch_key = None
-        self._index = None  # sample()'s staging for an uploaded index
+        self._index = _Staging(env, 4)  # sample()'s uploaded index
         h = ctypes.c_void_p()
         _lib.check(self._L.gc_replay_create(env._h, self.games, self.cap, self.max_plies,
                                             ctypes.c_int64(self.capacity), ctypes.byref(h)))
         self._h = h
-        addr = (ctypes.c_void_p * len(self.ARRAYS))()
-        _lib.check(self._L.gc_replay_pointers(self._h, addr, len(self.ARRAYS)))
-        self.ptr = {k: addr[i] for i, k in enumerate(self.ARRAYS)}
+        self.ptr = c_pointers(self._L.gc_replay_pointers, self._h, self.ARRAYS)
 
     def _shape(self, k):
         G, P, C_, R = self.games, self.max_plies, self.cap, self.capacity
@@ -1296,8 +964,11 @@ class SampleStore:
     def record(self, root):
         """the positions before the move and the roots' visit counts (gc_replay_record)"""
         if isinstance(root, _DeviceArrays):
-            v = root.ptr["target" if getattr(root, "gumbel", False) else "visits"]
-            a, rc = root.ptr["actions"], root._spec["actions"][1][-1]
+            visits = "target" if getattr(root, "gumbel", False) else "visits"
+            if "actions" not in root.ptr or visits not in root.ptr:  # (a rows / priors buffer, a DeviceIO)
+                raise TypeError(f"root: a root_policy() / gumbel_policy() result or (actions_ptr, visits_ptr, "
+                                f"row_cap); this {type(root).__name__} has no actions / {visits}")
+            a, v, rc = root.ptr["actions"], root.ptr[visits], root._spec["actions"][1][-1]
         else:
             a, v, rc = root
         _lib.check(self._L.gc_replay_record(self._h, int(a), int(v), int(rc)))
@@ -1329,16 +1000,11 @@ class SampleStore:
         rows = int(rows)
         if rows < 0:
             raise ValueError(f"rows {rows} < 0")
-        buf = planes if isinstance(planes, PlanesBuffer) else None
-        if buf is not None:
-            dtype, layout, row_stride = buf.dtype, buf.layout, buf.board_stride
-            if rows > buf.rows:
-                raise ValueError(f"{rows} rows, the planes buffer holds {buf.rows}")
-        if dtype not in env.POLICY_DTYPES:
-            raise ValueError(f"dtype must be one of {sorted(env.POLICY_DTYPES)}, got {dtype!r}")
-        if layout not in env.PLANES_LAYOUTS:
-            raise ValueError(f"layout must be one of {sorted(env.PLANES_LAYOUTS)}, got {layout!r}")
-        row_stride = int(env.PLANES * 64 if row_stride is None else row_stride)
+        if isinstance(planes, PlanesBuffer):  # the buffer's format, whatever the arguments say
+            dtype = layout = row_stride = None
+        buf, dtype, layout, row_stride = planes_format(planes, dtype, layout, row_stride, env.PLANES * 64)
+        if buf is not None and rows > buf.rows:
+            raise ValueError(f"{rows} rows, the planes buffer holds {buf.rows}")
         pi_stride = int(self.ROW if pi_stride is None else pi_stride)
         raw = PlanesBuffer._RAW[dtype]
         key = (rows, dtype, row_stride, planes is None, bool(dense), pi_stride)
@@ -1352,26 +1018,14 @@ class SampleStore:
                 spec["pi_dense"] = (np.float32, (rows, pi_stride))
             self._batch, self._batch_key = _DeviceArrays(env, spec), key
         b = self._batch
-        if planes is not None:
-            b.ptr["planes"] = buf.ptr if buf is not None else int(planes)
-            b._spec["planes"] = (raw, (rows, row_stride))
+        if planes is not None:  # the caller's memory: fetched with the batch, never freed by it
+            b.adopt("planes", buf.ptr if buf is not None else int(planes), raw, (rows, row_stride))
         if index is None:
             pidx = None
         elif isinstance(index, int):
             pidx = index or None
         else:
-            ix = np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
-            if ix.size != rows:
-                raise ValueError(f"{ix.size} slots for {rows} rows")
-            ix = np.clip(ix, -1, 2 ** 31 - 1).astype(np.int32)  # (anything out of range stays out of range)
-            if self._index is None or self._index._spec["index"][1][0] < max(rows, 1):
-                if self._index is not None:
-                    env.synchronize()
-                    self._index.close()
-                self._index = _DeviceArrays(env, {"index": (np.int32, (max(rows, 1),))})
-            pidx = self._index.ptr["index"]
-            if rows:
-                _lib.check(self._L.gc_env_copy(env._h, pidx, _lib.ptr(ix), ctypes.c_uint64(ix.nbytes), 1))
+            pidx, _ = upload_indices(self._index, index, rows, "{size} slots for {rows} rows")
         p = b.ptr
         _lib.check(self._L.gc_replay_sample(self._h, rows, pidx, ctypes.c_uint64(env.seed if seed is None else int(seed)),
                                             int(draw) & 0xFFFFFFFF, p["planes"], env.POLICY_DTYPES[dtype],
@@ -1385,8 +1039,6 @@ class SampleStore:
         if self._batch is not None:
             if self._h:
                 self.env.synchronize()  # (no launch still writes them)
-            if not self._batch_key[3]:
-                self._batch.ptr.pop("planes", None)
             self._batch.close()
             self._batch, self._batch_key = None, None
 
@@ -1403,105 +1055,19 @@ class SampleStore:
 
     def fetch(self, *keys):
         """host copies of the store's arrays (waits for the env's stream)"""
-        out = {}
-        for k in keys or self.ARRAYS:
-            a = np.zeros(self._shape(k), dtype=self._DTYPES.get(k, np.int32))
-            _lib.check(self._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
-            out[k] = a
-        return out
+        return fetch_arrays(self.env, self.ptr, keys or self.ARRAYS,
+                            lambda k: (self._DTYPES.get(k, np.int32), self._shape(k)))
 
     def device_bytes(self):
         return int(self._L.gc_replay_device_bytes(self._h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.gc_replay_destroy(self._h)  # (waits for the device)
+            self._L.gc_replay_destroy(self._h)  # (waits for the device; frees the arrays of ptr[...])
             self._h = None
             self._drop_batch()
-            if self._index is not None:
-                self._index.close()
-                self._index = None
+            self._index.close()
             self.ptr = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceIO:
-    """Device buffers of one env's step_device outputs: reward i32, done u8, reason u8 and
-    optionally mask u64[65][stride] (word-major: word f of board i at f * stride + i, stride >= N),
-    obs i8[N][64], count i32, pick u16 (the random policy's next action, which step_device uses
-    as the actions when given none), and with policy=True logprob f32 and entropy f32
-    (sample_policy's outputs).  fetch() copies them to host arrays; upload_actions() fills
-    the pick buffer from the host."""
-
-    _SPEC = {"reward": (np.int32, ()), "done": (np.uint8, ()), "reason": (np.uint8, ()),
-             "mask": (np.uint64, (65,)), "obs": (np.int8, (64,)), "count": (np.int32, ()), "pick": (np.uint16, ()),
-             "logprob": (np.float32, ()), "entropy": (np.float32, ())}
-
-    @staticmethod
-    def default_mask_stride(n):
-        """From N = 4096 on: N rounded up to a multiple of 512, plus GC_MASK_PAD words (default
-        MASK_PAD).  Packed rows of N = 65 536 sit 512 KiB apart and fall on the same HBM
-        channels; measured on the quad API step (same box): packed 17.0 us per launch, padded by
-        8 words 16.4, by 64 16.2, by 256-4096 15.6-15.8 -- 512 (4 KiB) kept; N = 65 472 packed
-        (511.5 KiB apart) 16.8 against 16.2 for 65 536 padded."""
-        pad = int(os.environ.get("GC_MASK_PAD", DeviceIO.MASK_PAD))
-        return (n + 511) // 512 * 512 + pad if n >= 4096 and pad else n
-
-    MASK_PAD = 512
-
-    def __init__(self, env, mask=True, obs=True, count=True, pick=True, select=True, mask_stride=None,
-                 policy=False):
-        self.env = env
-        n = env.num_boards
-        self.mask_stride = int(self.default_mask_stride(n) if mask_stride is None else mask_stride)
-        if self.mask_stride < n:
-            raise ValueError(f"mask_stride {self.mask_stride} < num_boards {n}")
-        want = {"reward": True, "done": True, "reason": True, "mask": mask, "obs": obs, "count": count, "pick": pick,
-                "logprob": policy, "entropy": policy}
-        self.ptr = {}
-        for k, on in want.items():
-            if not on:
-                continue
-            dt, sh = self._SPEC[k]
-            rows = self.mask_stride if k == "mask" else n
-            nb = rows * int(np.prod(sh, dtype=np.int64)) * np.dtype(dt).itemsize
-            v = ctypes.c_void_p()
-            _lib.check(env._L.gc_device_alloc(env.device, ctypes.c_uint64(nb), ctypes.byref(v)))
-            self.ptr[k] = v.value
-        if pick and select:  # the policy's picks for the current states
-            self.select()
-
-    def select(self):
-        """pick = the env's current random-policy actions (picked at creation, reset(),
-        step_random(), rollout(); after set_states / set_fens call env.select_random() first)"""
-        self.upload_actions(self.env.outputs()["next_action"])
-
-    def upload_actions(self, actions):
-        a = np.ascontiguousarray(actions, dtype=np.uint16).reshape(self.env.num_boards)
-        _lib.check(self.env._L.gc_env_copy(self.env._h, self.ptr["pick"], _lib.ptr(a), ctypes.c_uint64(a.nbytes), 1))
-
-    def fetch(self, *keys):
-        """host copies; the mask comes back as [N][65] (the device buffer is word-major
-        [65][mask_stride])"""
-        out = {}
-        n = self.env.num_boards
-        for k in keys or self.ptr:
-            dt, sh = self._SPEC[k]
-            shape = (65, self.mask_stride) if k == "mask" else (n,) + sh
-            a = np.zeros(shape, dtype=dt)
-            _lib.check(self.env._L.gc_env_copy(self.env._h, _lib.ptr(a), self.ptr[k], ctypes.c_uint64(a.nbytes), 2))
-            out[k] = np.ascontiguousarray(a[:, :n].T) if k == "mask" else a
-        return out
-
-    def close(self):
-        for v in self.ptr.values():
-            self.env._L.gc_device_free(self.env.device, ctypes.c_void_p(v))
-        self.ptr = {}
 
     def __del__(self):
         try:
