@@ -22,6 +22,10 @@ Outputs (data only -- inputs + expected outputs, no reference source):
                            invalid actions; opponent "none" and "random")
   v2_setter_traces.json.gz ChessEnvV2 with state assignments between steps: outputs and
                            the whole saved_boards dict after every step
+  v1_fuzz.json.gz          (made by make_v1_fuzz.py with this module's loader and filters) the v1
+                           engine on fuzzed boards in five families -- sparse, castle, pawns,
+                           checks, late: ordered lists, EVERY listed move's next board, reward
+                           and check flags, perft(1..3) with the rights off
 
 Usage:  python tests/golden/make_golden.py [--deep]
 """
