@@ -1,16 +1,12 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes view of apply_split_host.cpp (the two halves of the
-branch-free apply of gc_core.h against apply_legal), built as corehost.py builds its library."""
+branch-free apply of gc_core.h against apply_legal), built by _hostlib.py."""
 import ctypes
-import hashlib
-import os
-import subprocess
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "apply_split_host.cpp")
-_SO = os.path.join(_HERE, "_build", "libapplysplithost.so")
-_STAMP = _SO + ".srchash"
-_CSRC = os.path.join(_HERE, "..", "..", "gym-chess_amd", "csrc")
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas"]
+try:
+    from . import _hostlib  # imported as core_host.applysplithost
+except ImportError:
+    import _hostlib  # imported from this directory
+
 _L = None
 P = ctypes.c_void_p
 CASES = ("castle_ksw", "castle_qsw", "castle_ksb", "castle_qsb", "capture_queen", "capture_rook", "capture_bishop",
@@ -18,34 +14,15 @@ CASES = ("castle_ksw", "castle_qsw", "castle_ksb", "castle_qsb", "capture_queen"
          "moves")
 
 
-def source_hash():
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    for path in [_SRC] + sorted(os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h")):
-        h.update(os.path.basename(path).encode() + b"\0")
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
-
-
 def ensure_built():
-    """(re)build libapplysplithost.so unless its stamp holds the current source hash"""
-    want = source_hash()
-    if os.path.exists(_SO) and os.path.exists(_STAMP) and open(_STAMP).read().strip() == want:
-        return
-    os.makedirs(os.path.dirname(_SO), exist_ok=True)
-    tmp = f"{_SO}.{os.getpid()}.tmp"  # build aside, then rename (parallel test workers)
-    subprocess.run(["g++"] + FLAGS + ["-o", tmp, _SRC], check=True)
-    os.replace(tmp, _SO)
-    with open(f"{_STAMP}.{os.getpid()}.tmp", "w") as f:
-        f.write(want)
-    os.replace(f"{_STAMP}.{os.getpid()}.tmp", _STAMP)
+    """(re)build libapplysplithost.so unless its stamp holds the current source hash; -> its path"""
+    return _hostlib.ensure_built("apply_split_host.cpp", "libapplysplithost.so")
 
 
 def lib():
     global _L
     if _L is None:
-        ensure_built()
-        L = ctypes.CDLL(_SO)
+        L = ctypes.CDLL(ensure_built())
         L.as_compare.argtypes = [P, P, P, ctypes.c_int, P, P]
         _L = L
     return _L

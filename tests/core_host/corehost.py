@@ -1,53 +1,27 @@
 """TEST INFRASTRUCTURE ONLY -- ctypes view of the host build of the product's bitboard core
 (gym-chess_amd/csrc/gc_core.h + gc_env.h compiled by g++), for CPU differential tests."""
 import ctypes
-import hashlib
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "_build", "libcorehost.so")
-_STAMP = _SO + ".srchash"
-_CSRC = os.path.join(_HERE, "..", "..", "gym-chess_amd", "csrc")
-FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas"]
+try:
+    from . import _hostlib  # imported as core_host.corehost
+except ImportError:
+    import _hostlib  # imported from this directory
+
 _L = None
 P = ctypes.c_void_p
 
 
-def source_hash():
-    """sha256 prefix of core_host.cpp, the product's device headers it compiles and the flags
-    (content, not mtimes: a library built from other sources is never reused)"""
-    h = hashlib.sha256(" ".join(FLAGS).encode())
-    srcs = [os.path.join(_HERE, "core_host.cpp")] + sorted(
-        os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h"))
-    for path in srcs:
-        h.update(os.path.basename(path).encode() + b"\0")
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
-
-
 def ensure_built():
-    """(re)build libcorehost.so unless its stamp holds the current source hash"""
-    want = source_hash()
-    if os.path.exists(_SO) and os.path.exists(_STAMP) and open(_STAMP).read().strip() == want:
-        return
-    os.makedirs(os.path.dirname(_SO), exist_ok=True)
-    tmp = f"{_SO}.{os.getpid()}.tmp"  # build aside, then rename: parallel test workers never load a partial file
-    subprocess.run(["g++"] + FLAGS + ["-o", tmp, os.path.join(_HERE, "core_host.cpp")], check=True)
-    os.replace(tmp, _SO)
-    with open(f"{_STAMP}.{os.getpid()}.tmp", "w") as f:
-        f.write(want)
-    os.replace(f"{_STAMP}.{os.getpid()}.tmp", _STAMP)
+    """(re)build libcorehost.so unless its stamp holds the current source hash; -> its path"""
+    return _hostlib.ensure_built("core_host.cpp", "libcorehost.so")
 
 
 def lib():
     global _L
     if _L is None:
-        ensure_built()
-        L = ctypes.CDLL(_SO)
+        L = ctypes.CDLL(ensure_built())
         L.host_between.restype = ctypes.c_uint64
         L.host_pins_agree.argtypes = [P, P, ctypes.c_int]
         L.host_count_moves_agree.argtypes = [P, P, ctypes.c_int]

@@ -21,7 +21,7 @@ extern "C" void so_origin(const uint64_t* occ, const uint8_t* white, const int32
     }
 }
 
-// The makers of the fused ply's count words (gymchess.hip quad_ply): Q0 the pawn and knight sets,
+// The makers of the fused ply's count words (gc_quad.h quad_ply): Q0 the pawn and knight sets,
 // Q2 the rook / queen and king sets, Q3 the bishop / queen sets.
 static int maker_of(int set) { return set < SW_ORTH ? 0 : set < SW_DIAG ? 1 : set < SW_K ? 2 : 1; }
 

@@ -32,7 +32,7 @@ wg1 = os.environ.get("PST_WG") == "1"
 waves = ((n + 63) // 64) * 4 if quad and wg1 else ((n + 127) // 128) * (8 if quad else 4)
 out = np.zeros(waves * 12, dtype=np.uint64)
 run = np.zeros(waves * 2, dtype=np.uint64)  # the quad rollout's Q1: plies with an in-loop window load, their phase 2
-PST_BINS, PST_BIN_CYCLES = 16, 128  # gymchess.hip
+PST_BINS, PST_BIN_CYCLES = 16, 128  # gc_stamps.h
 last = np.zeros(waves * 4 * (PST_BINS + 1), dtype=np.uint32)  # who arrived last at each barrier, by margin
 if quad and wg1 and hasattr(L, "gc_debug_pstamps2"):
     L.gc_debug_pstamps2.argtypes = [P, ctypes.c_int, P, P, P]
