@@ -275,8 +275,9 @@ GC_HD int env_ply(Pos& s, H& hist, int action, Gen& g, MoveSet& ms, S& scr, int*
 // One step() (chess_v2.py:219-294, opponent="none").  On return with o.moved, `g`/`ms`/`scr`
 // describe the new position (side now to move) so the caller can pick the next action
 // without regenerating.  `g0` must be gen_init(s) when VALIDATE (external actions); the
-// on-device policy is trusted.
-template <bool VALIDATE, class H, class S>
+// on-device policy is trusted.  GEN as env_ply's: 1 = `ms` holds the count only (a caller that
+// picks set-wise from `g`, gc_playout.h).
+template <bool VALIDATE, int GEN = 2, class H, class S>
 GC_HD StepOut env_step(Pos& s, H& hist, int action, const Gen* g0, Gen& g, MoveSet& ms, S& scr) {
     StepOut o = {0, 0, R_NONE, 0};
     if (VALIDATE && !action_legal(s, *g0, action)) {  // chess_v2.py:240-242
@@ -290,7 +291,7 @@ GC_HD StepOut env_step(Pos& s, H& hist, int action, const Gen* g0, Gen& g, MoveS
     bool white = s.meta & M_WHITE;
     int mr;
     bool rep, opp_chk;
-    int rc = env_ply(s, hist, action, g, ms, scr, &mr, &rep, &opp_chk);
+    int rc = env_ply<GEN>(s, hist, action, g, ms, scr, &mr, &rep, &opp_chk);
     if (rc == 1) {
         o.reason = R_BOTH_CHECKED;
         o.done = 1;
@@ -322,13 +323,17 @@ struct PolicyCtx {
 // The random self-play policy (opponent "none", reference rules): rank k drawn uniformly over
 // the legal moves, the k-th in move-set order (gc_core.h sw_gen / sw_select), generated here
 // set-wise from the position.  A_NONE (no draw taken) when there is no legal move.
-GC_HD int selfplay_pick(const Pos& s, PolicyCtx& pc) {
-    Gen g;
-    gen_init(s, g);
+// (selfplay_pick_gen: with g = gen_init(s) already at hand, as env_step leaves it after a move)
+GC_HD int selfplay_pick_gen(const Pos& s, const Gen& g, PolicyCtx& pc) {
     u64 t[SW_SETS];
     const int n = sw_gen(s, g, t);
     if (n == 0) return A_NONE;
     return sw_select(g, t, (int)policy_index(pc.seed, pc.board, pc.draw++, (u32)n));
+}
+GC_HD int selfplay_pick(const Pos& s, PolicyCtx& pc) {
+    Gen g;
+    gen_init(s, g);
+    return selfplay_pick_gen(s, g, pc);
 }
 
 // step() with the random opponent (chess_v2.py:219-294 with opponent_policy set): the

@@ -3826,6 +3826,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_clone.h"
 #include "gc_tree.h"
 #include "gc_replay.h"
+#include "gc_playout.h"
 
 // ----------------------------------------------------------------------------- host side (the C ABI)
 #include "gc_fen.h"
@@ -3838,4 +3839,5 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_host_clone.h"
 #include "gc_host_tree.h"
 #include "gc_host_replay.h"
+#include "gc_host_playout.h"
 #include "gc_host_ckpt.h"

@@ -2,7 +2,7 @@
 
     _DeviceArrays   named device arrays, owned (allocated here, freed by close() / __del__) or
                     adopted (someone else's address: fetched like the others, never freed)
-    RowsBuffer, PriorsBuffer, DeviceIO, _GumbelPolicy   subclasses: their spec and what is their own
+    RowsBuffer, PriorsBuffer, PlayoutBuffer, DeviceIO, _GumbelPolicy   subclasses: their spec and what is their own
     PlanesBuffer, TraceBuffer   one owned array whose `ptr` is the address itself
     _Staging        the grow-by-doubling upload buffer; upload_indices fills it with a host index list
 
@@ -145,6 +145,18 @@ class PriorsBuffer(_DeviceArrays):
         keys = ("actions", "priors", "count") + (("logit_index",) if logit_index else ())
         super().__init__(env, {k: (self._SPEC[k], (self.rows,) if k == "count" else (self.rows, self.cap))
                                for k in keys})
+
+
+class PlayoutBuffer(_DeviceArrays):
+    """Device memory of a playout run's outputs: value float32[rows] (the mean outcome from the
+    view of the side to move at the board) and tally int32[rows][6] (wins, losses, other endings,
+    cut-offs, the cut-offs' material sum, plies played); ptr[...] are device pointers."""
+
+    TALLY = ("wins", "losses", "others", "cutoffs", "material", "plies")
+
+    def __init__(self, env, rows):
+        self.rows = _rows(rows)
+        super().__init__(env, {"value": (np.float32, (self.rows,)), "tally": (np.int32, (self.rows, len(self.TALLY)))})
 
 
 class DeviceIO(_DeviceArrays):

@@ -25,8 +25,9 @@ import numpy as np
 from . import _lib
 from . import buffers as B
 from . import codec as C
-from .buffers import (DeviceIO, PlanesBuffer, PriorsBuffer, RowsBuffer, TraceBuffer, _DeviceArrays,  # noqa: F401
-                      _GumbelPolicy, _Staging, c_pointers, fetch_arrays, planes_format, upload, upload_indices)
+from .buffers import (DeviceIO, PlanesBuffer, PlayoutBuffer, PriorsBuffer, RowsBuffer, TraceBuffer,  # noqa: F401
+                      _DeviceArrays, _GumbelPolicy, _Staging, c_pointers, fetch_arrays, planes_format, upload,
+                      upload_indices)
 
 REASONS = {0: "none", 1: "mate", 2: "repetition", 3: "move_cap", 4: "no_moves", 5: "both_kings_checked",
            6: "invalid_action", 7: "already_done", 8: "mated_by_opponent", 9: "opponent_no_move",
@@ -42,7 +43,8 @@ class BatchedChessEnv:
         self.seed = int(seed)
         # the uploaded lists of policy_priors (int32 boards), step_boards / encode_planes_rows (int32
         # boards + uint16 actions) and clone_boards (2 x int32 indices); step_boards' own rows buffer
-        self._staging = {"priors": _Staging(self, 4), "rows": _Staging(self, 6), "clone": _Staging(self, 8)}
+        self._staging = {"priors": _Staging(self, 4), "rows": _Staging(self, 6), "clone": _Staging(self, 8),
+                         "playouts": _Staging(self, 4)}
         self._rows_out = None
         ib = None
         if initial_board is not None:
@@ -74,6 +76,11 @@ class BatchedChessEnv:
                 if st is not None:
                     st.close()
             self._stores = []
+            for ref in getattr(self, "_playouts", ()):  # and playout handles
+                po = ref()
+                if po is not None:
+                    po.close()
+            self._playouts = []
             for st in self._staging.values():
                 st.close()
             if self._rows_out is not None:
@@ -562,6 +569,18 @@ class BatchedChessEnv:
             self._stores = []
         self._stores.append(weakref.ref(st))
         return st
+
+    # ------------------------------------------------------------------ random-playout leaf values
+    def playouts(self, max_rows, playouts=8, max_plies=64):
+        """A random-playout evaluator on this env's boards (gc_playout_*): per listed board
+        `playouts` (1, 2, 4, ..., 64) bounded random playouts of up to `max_plies` (<= 128) plies
+        from a private copy, and the mean outcome -- a search's leaf values without a network.
+        Reference rules, opponent "none".  See Playouts."""
+        po = Playouts(self, max_rows, playouts=playouts, max_plies=max_plies)
+        if not hasattr(self, "_playouts"):
+            self._playouts = []
+        self._playouts.append(weakref.ref(po))
+        return po
 
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""
@@ -1074,6 +1093,74 @@ class SampleStore:
             self.close()
         except Exception:
             pass
+
+
+class Playouts(PlayoutBuffer):
+    """Random-playout leaf values on the device (gc_playout_*, gym-chess_amd/csrc/gc_playout.h).
+
+        res = run(boards, ...)   ONE launch, asynchronous on the env's stream: row j plays `playouts`
+                                 random playouts of `plies` plies from a private copy of board
+                                 boards[j] (its 3-fold window starts empty) and writes
+                                 res.value float32[rows] -- (wins - losses + cut_weight * material / 16)
+                                 / playouts, in [-1, 1] from the view of the side to move at the
+                                 board, what SearchTree.backup takes for a new leaf -- and res.tally
+                                 int32[rows][6] (PlayoutBuffer.TALLY); the env is not written
+        fetch()                  host copies of this object's own value / tally (waits for the stream)
+
+    This object is also the default output buffer (max_rows rows): run() returns it unless given
+    out=, a playout_buffer()."""
+
+    def __init__(self, env, max_rows, playouts=8, max_plies=64):
+        self._h = None
+        self.max_rows, self.playouts, self.max_plies = int(max_rows), int(playouts), int(max_plies)
+        self._L = env._L
+        h = ctypes.c_void_p()
+        _lib.check(self._L.gc_playout_create(env._h, self.max_rows, self.playouts, self.max_plies, ctypes.byref(h)))
+        self._h = h
+        super().__init__(env, self.max_rows)
+
+    def playout_buffer(self, rows=None):
+        """another output buffer for run(out=...): value float32[rows], tally int32[rows][6]"""
+        return PlayoutBuffer(self.env, self.max_rows if rows is None else rows)
+
+    def run(self, boards=None, rows=None, plies=None, seed=None, draw=0, cut_weight=1.0, out=None):
+        """boards: None = boards 0..rows-1 (rows defaults to max_rows); an array-like of board
+        indices (uploaded to a staging buffer of the env on its stream, a synchronous copy as
+        clone_boards') or a device pointer (int) to int32[rows], with rows.  Duplicates are fine; an
+        index outside [0, N) -- a search's -1 rows -- and a board that is done give value 0 and a
+        zero tally.  plies: None = max_plies.  The playouts draw from the Philox stream (seed,
+        row * playouts + p, draw + ply): seed None = the env's; the caller advances draw (by at
+        least plies) between calls that should differ.  cut_weight in [0, 1] weighs the material
+        term of the playouts cut off after `plies` plies.  Returns the buffer written (out, or
+        this object)."""
+        env = self.env
+        if boards is None:
+            pb, m = None, self.max_rows if rows is None else int(rows)
+        elif isinstance(boards, int):
+            if rows is None:
+                raise ValueError("a device pointer needs rows")
+            pb, m = boards or None, int(rows)
+        else:
+            pb, m = upload_indices(env._staging["playouts"], boards, rows)
+        out = self if out is None else out
+        if not isinstance(out, PlayoutBuffer):
+            raise TypeError("out must be a playout_buffer()")
+        if m > out.rows:
+            raise ValueError(f"{m} rows, the playout buffer holds {out.rows}")
+        _lib.check(self._L.gc_playout_run(self._h, pb, m, self.max_plies if plies is None else int(plies),
+                                          ctypes.c_uint64(env.seed if seed is None else int(seed)),
+                                          int(draw) & 0xFFFFFFFF, float(cut_weight), out.ptr["value"], out.ptr["tally"]))
+        return out
+
+    def device_bytes(self):
+        """the private windows' allocation (the outputs not counted)"""
+        return int(self._L.gc_playout_device_bytes(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gc_playout_destroy(self._h)  # (waits for the device: no launch still writes the outputs)
+            self._h = None
+        super().close()
 
 
 class MultiDeviceChessEnv:

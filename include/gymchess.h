@@ -723,6 +723,58 @@ int gc_replay_sample(gc_replay* r, int rows, const int32_t* d_index, uint64_t se
 int gc_replay_counters(gc_replay* r, uint64_t* total, uint64_t* live, uint64_t* plies, uint64_t* dropped);
 int gc_replay_pointers(gc_replay* r, void** out, int n);
 uint64_t gc_replay_device_bytes(gc_replay* r);
+/* Random-playout leaf values (gc_playout.h): for a device list of boards of `e`, P bounded random
+ * playouts per board from a private copy of its position, and the mean outcome -- the value a
+ * search needs per leaf when there is no network (classic MCTS), in the shape of the calls around
+ * it (gc_env_encode_planes_rows, gc_env_policy_priors).  `e` is any env under the reference rules
+ * with opponent "none"; a FIDE env and an env whose opponent replies inside the step are out of
+ * scope here and refused with a message.  `e` must outlive the handle.
+ * gc_playout_create: playouts (P) one of 1, 2, 4, 8, 16, 32, 64; 1 <= max_plies <= 128;
+ * max_rows >= 1, max_rows * P <= 2^30.  One allocation, zeroed once on e's stream, for the lanes'
+ * private 3-fold windows: per lane a table of 256 entries of 64 bytes (load <= 0.5 at 128 plies;
+ * the entry header has no room for the key tag of a smaller table) and a generation word,
+ *     gc_playout_device_bytes = roundup(max_rows * P, 64) * (256 * 64 + 4)
+ * -- 128 MiB at max_rows 1 024, P 8.  A run bumps every lane's generation, so nothing is cleared
+ * between calls and the entries of earlier calls are dead.
+ * gc_playout_run: ONE launch, asynchronous on e's stream, no host synchronisation, no atomics.
+ * d_board_idx: DEVICE int32[rows], NULL = boards 0..rows-1.  0 <= rows <= max_rows (rows == 0
+ * succeeds and launches nothing), 1 <= n_plies <= max_plies, cut_weight finite in [0, 1]; either
+ * output may be NULL.  For row j, board b = d_board_idx[j]:
+ *   skipped   b outside [0, gc_env_num_boards(e)), or a board whose state is done: value 0.0f, an
+ *             all-zero tally.  Whatever the index array holds, every access stays in bounds.
+ *   playout   p in 0..P-1 is lane L = j * P + p.  It starts from a copy of board b's position with
+ *             an EMPTY repetition window (window length 0): positions before the leaf do not count
+ *             towards a 3-fold inside a playout.  At ply t = 0, 1, ... the action is the env's own
+ *             random self-play pick -- rank policy_index(seed, L, draw + t, n) over the n legal
+ *             moves, the k-th in move-set order (gc_env_step_random's policy) -- applied with the
+ *             semantics of one env step without validation: rights forcing, both kings checked,
+ *             the move cap (the board's move_count carries over), the 3-fold on the pre-move board,
+ *             mate, the move_count advance.
+ *   ending    the first of: reason 1 (mate) at ply t -- a WIN if t is even (the side to move at the
+ *             start delivered it), else a LOSS; any other done of the step (repetition, move cap,
+ *             both kings checked, window full) or a position with no legal move (nothing picked,
+ *             no draw taken) -- an OTHER ending, worth 0; n_plies plies played -- a CUT-OFF with
+ *             the material term m = clamp(d, -16, 16), d = sum over piece types of value *
+ *             (popcount(own) - popcount(enemy)), own = the side to move at the start, values Q 10,
+ *             R 5, B 3, N 3, P 1 (the step's capture values).
+ *   d_tally   i32 [rows][6], exact integers: 0 wins, 1 losses, 2 other endings, 3 cut-offs, 4 the
+ *             sum of m over the cut-offs, 5 the sum of plies played (env steps taken; a step that
+ *             ends the playout counts).
+ *   d_value   f32 [rows], in this order of operations, each rounded to fp32:
+ *             ((float)(wins - losses) + cut_weight * ((float)tally4 * 0.0625f)) / (float)P
+ *             in [-1, 1], from the view of the side to move at board b -- the view
+ *             gc_tree_backup's d_value takes for a new leaf.
+ * Nothing of `e` is written: states, windows and generations, draw counters, outputs and policy
+ * actions stay.  A run is a function of the boards' positions, seed, draw, P and n_plies.
+ * Every call fails with nothing launched on a NULL handle (create: e, out), arguments outside the
+ * limits above, and an env that create would refuse (gc_env_set_rules / gc_env_set_opponent can
+ * change an env after the handle exists). */
+typedef struct gc_playout gc_playout;
+int gc_playout_create(gc_env* e, int max_rows, int playouts, int max_plies, gc_playout** out);
+int gc_playout_destroy(gc_playout* p);
+int gc_playout_run(gc_playout* p, const int32_t* d_board_idx, int rows, int n_plies, uint64_t seed, uint32_t draw,
+                   float cut_weight, float* d_value, int32_t* d_tally);
+uint64_t gc_playout_device_bytes(gc_playout* p);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
