@@ -82,6 +82,7 @@ static int engine_reserve(gc_engine* e, int n, int listcap) {
         return -1;
     hipError_t he = hipHostMalloc((void**)&e->hio, io, hipHostMallocDefault);
     if (he != hipSuccess) return fail(std::string("hipHostMalloc: ") + hipGetErrorString(he));
+    host_fill(e->hio, io);
     e->io_cap = io;
     e->cap_n = nn;
     e->cap_list = lc;
@@ -94,6 +95,7 @@ static int engine_stage(gc_engine* e, int n, int lc, const int8_t* boards, const
     e->zc_on = engine_zc_enabled() && engine_offsets((size_t)n, (size_t)lc).end <= ENGINE_ZC_BYTES;
     if (e->zc_on && !e->zc) {
         HIPCHK(hipHostMalloc((void**)&e->zc, ENGINE_ZC_BYTES, hipHostMallocMapped | hipHostMallocCoherent));
+        host_fill(e->zc, ENGINE_ZC_BYTES);
         HIPCHK(hipHostGetDevicePointer((void**)&e->zcd, e->zc, 0));
     }
     uint8_t* h = e->zc_on ? e->zc : e->hio;

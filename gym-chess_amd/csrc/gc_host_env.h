@@ -212,7 +212,10 @@ extern "C" int gc_env_create(int device, int n_boards, uint64_t seed, const int8
         // the completion word of the quad rollout (host-mapped, fine-grained)
         u32* hw = nullptr;
         he = hipHostMalloc(&hw, 4, hipHostMallocMapped | hipHostMallocCoherent);
-        if (he == hipSuccess) { e->done_host = hw; *hw = 0; he = hipMalloc(&e->done_dev, 8); }
+        if (he == hipSuccess) { e->done_host = hw; host_fill(hw, 4); *hw = 0; }
+        if (he == hipSuccess && dalloc(&e->done_dev, 2)) {
+            std::string m = g_err; env_free(e); delete e; return fail(m);
+        }
         if (he == hipSuccess) he = hipMemsetAsync(e->done_dev, 0, 8, e->stream);
         u32* hwd = nullptr;
         if (he == hipSuccess) he = hipHostGetDevicePointer((void**)&hwd, hw, 0);
@@ -331,6 +334,7 @@ extern "C" int gc_env_single_setup(gc_env* e, int agent_white) {
     if (set_window_kind(e, !agent_white)) return -1;
     if (!e->srec) {
         HIPCHK(hipHostMalloc(&e->srec, sizeof(gc_single_record), hipHostMallocMapped));
+        host_fill(e->srec, sizeof(gc_single_record));
         HIPCHK(hipHostGetDevicePointer((void**)&e->srec_d, e->srec, 0));
     }
     return 0;
@@ -746,7 +750,13 @@ extern "C" int gc_env_get_stream(gc_env* e, void** stream) {
 extern "C" int gc_device_alloc(int device, uint64_t bytes, void** ptr) {
     if (!ptr) return fail("null argument");
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(ptr, bytes ? bytes : 1));
+    return dalloc(reinterpret_cast<uint8_t**>(ptr), (size_t)bytes);
+}
+// GC_ALLOC_FILL's effect since load: the allocations filled and their bytes
+extern "C" int gc_alloc_fill_stats(uint64_t* allocs, uint64_t* bytes) {
+    if (!allocs || !bytes) return fail("null argument");
+    *allocs = g_fill_allocs.load();
+    *bytes = g_fill_bytes.load();
     return 0;
 }
 extern "C" int gc_device_free(int device, void* ptr) {

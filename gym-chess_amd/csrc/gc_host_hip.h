@@ -11,11 +11,49 @@ static inline int grid_for(int n) { return (n + BLOCK - 1) / BLOCK; }
 // one lane per slot of a table of `slots` entries
 static inline unsigned grid_for_slots(size_t slots) { return (unsigned)((slots + BLOCK - 1) / BLOCK); }
 
+// GC_ALLOC_FILL=<hex byte> (per call; tests): every fresh device or pinned host allocation is
+// filled with that byte before it is handed out, so a read of memory nothing wrote shows as a
+// wrong result instead of the zeroes a fresh process usually gets.  -1: unset (or not a byte).
+static std::atomic<unsigned long long> g_fill_allocs{0}, g_fill_bytes{0};
+static int alloc_fill_byte() {
+    const char* s = getenv("GC_ALLOC_FILL");
+    if (!s || !*s) return -1;
+    char* end = nullptr;
+    const unsigned long v = strtoul(s, &end, 16);
+    return (end == s || *end || v > 0xFF) ? -1 : (int)v;
+}
+static void alloc_fill_count(size_t bytes) {
+    g_fill_allocs++;
+    g_fill_bytes += bytes;
+}
+// a fresh device buffer: the fill is complete on return, whichever stream the caller uses next
+static int dev_fill(void* p, size_t bytes) {
+    const int fb = alloc_fill_byte();
+    if (fb < 0) return 0;
+    hipError_t e = hipMemset(p, fb, bytes);  // (the null stream; the library's own are non-blocking)
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return fail(std::string("alloc fill: ") + hipGetErrorString(e));
+    alloc_fill_count(bytes);
+    return 0;
+}
+// its twin for a fresh hipHostMalloc'd buffer (the explicit initial stores follow it)
+static void host_fill(void* p, size_t bytes) {
+    const int fb = alloc_fill_byte();
+    if (fb < 0) return;
+    memset(p, fb, bytes);
+    alloc_fill_count(bytes);
+}
+
 template <class T>
 static int dalloc(T** p, size_t count) {
     if (count == 0) count = 1;
     hipError_t e = hipMalloc((void**)p, count * sizeof(T));
     if (e != hipSuccess) return fail(std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (dev_fill(*p, count * sizeof(T))) {
+        (void)hipFree(*p);
+        *p = nullptr;
+        return -1;
+    }
     return 0;
 }
 

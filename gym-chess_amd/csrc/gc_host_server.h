@@ -135,6 +135,7 @@ struct SrvClient {
         if (devsrv_claim(s, owner, stop_fn)) return -1;
         if (!box) {
             HIPCHK(hipHostMalloc((void**)&box, sizeof(Box), hipHostMallocMapped | hipHostMallocCoherent));
+            host_fill(box, sizeof(Box));
             memset(box, 0, sizeof(Box));
             HIPCHK(hipHostGetDevicePointer((void**)&box_d, box, 0));
             HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));

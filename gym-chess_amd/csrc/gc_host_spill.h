@@ -81,7 +81,10 @@ static int spill_alloc(gc_env* e, int bits) {
     if (tmps.alloc(&t.ent, (size_t)8 << bits) || tmps.alloc(&t.ctr, 4)) return -1;
     hipError_t he = hipMemsetAsync(t.ent, 0, (size_t)64 << bits, e->stream);
     if (he == hipSuccess) he = hipMemsetAsync(t.ctr, 0, 16, e->stream);
-    if (he == hipSuccess && !e->sp_ctr_h) he = hipHostMalloc(&e->sp_ctr_h, 16, hipHostMallocDefault);
+    if (he == hipSuccess && !e->sp_ctr_h) {
+        he = hipHostMalloc(&e->sp_ctr_h, 16, hipHostMallocDefault);
+        if (he == hipSuccess) host_fill(e->sp_ctr_h, 16);
+    }
     if (he == hipSuccess && !e->sp_ev) he = hipEventCreateWithFlags(&e->sp_ev, hipEventDisableTiming);
     if (he != hipSuccess) return fail(std::string("spill table: ") + hipGetErrorString(he));
     if (e->d.ic.spill.ent) (void)hipFree(e->d.ic.spill.ent);

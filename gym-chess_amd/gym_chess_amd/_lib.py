@@ -129,6 +129,7 @@ SIGNATURES = {
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),
     "gc_device_free": (_I, [_I, _P]),
+    "gc_alloc_fill_stats": (_I, [_P, _P]),
     "gc_env_copy": (_I, [_P, _P, _P, _U64, _I]),
     "gc_env_rollout": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "gc_env_rollout_device": (_I, [_P, _I, _P, _I, _I]),

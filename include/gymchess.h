@@ -781,6 +781,11 @@ int gc_env_get_stream(gc_env* e, void** stream);
 int gc_device_alloc(int device, uint64_t bytes, void** ptr);
 int gc_device_free(int device, void* ptr);
 int gc_env_copy(gc_env* e, void* dst, const void* src, uint64_t bytes, int kind);
+/* GC_ALLOC_FILL=<hex byte> (read per allocation; a test aid): every fresh device buffer of the
+ * library (gc_device_alloc included) and every pinned host buffer is filled with that byte
+ * before it is handed out, the fill complete on return.  The allocations filled and their bytes
+ * since the library was loaded (both stay put while the variable is unset): */
+int gc_alloc_fill_stats(uint64_t* allocs, uint64_t* bytes);
 /* Device-resident random self-play (the test_benchmark.py driver): n_plies one-ply kernel
  * launches; each ply = one env.step() with a uniform Philox pick over the legal list, a
  * reset when done, a reset without a step when the list is empty (reason 4).  The policy's
