@@ -3827,6 +3827,7 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_tree.h"
 #include "gc_replay.h"
 #include "gc_playout.h"
+#include "gc_minimax.h"
 
 // ----------------------------------------------------------------------------- host side (the C ABI)
 #include "gc_fen.h"
@@ -3840,4 +3841,5 @@ __global__ void __launch_bounds__(BLOCK) k_fenv_step_api(EnvDev e, const uint16_
 #include "gc_host_tree.h"
 #include "gc_host_replay.h"
 #include "gc_host_playout.h"
+#include "gc_host_minimax.h"
 #include "gc_host_ckpt.h"

@@ -2,7 +2,8 @@
 
     _DeviceArrays   named device arrays, owned (allocated here, freed by close() / __del__) or
                     adopted (someone else's address: fetched like the others, never freed)
-    RowsBuffer, PriorsBuffer, PlayoutBuffer, DeviceIO, _GumbelPolicy   subclasses: their spec and what is their own
+    RowsBuffer, PriorsBuffer, PlayoutBuffer, MinimaxBuffer, DeviceIO, _GumbelPolicy
+                    subclasses: their spec and what is their own
     PlanesBuffer, TraceBuffer   one owned array whose `ptr` is the address itself
     _Staging        the grow-by-doubling upload buffer; upload_indices fills it with a host index list
 
@@ -157,6 +158,24 @@ class PlayoutBuffer(_DeviceArrays):
     def __init__(self, env, rows):
         self.rows = _rows(rows)
         super().__init__(env, {"value": (np.float32, (self.rows,)), "tally": (np.int32, (self.rows, len(self.TALLY)))})
+
+
+class MinimaxBuffer(_DeviceArrays):
+    """Device memory of minimax's outputs: pick uint16[rows] (0xFFFF: no move), score int32[rows],
+    value float32[rows] (from the view of the side to move at the board), count int32[rows], nodes
+    uint32[rows] (written only by a call with nodes=True) and, with cap > 0, the root lists actions
+    uint16[rows][cap] / scores int32[rows][cap] (padding 0xFFFF / INT32_MIN); ptr[...] are device
+    pointers."""
+
+    def __init__(self, env, rows, cap=0):
+        self.rows, self.cap = _rows(rows), int(cap)
+        if not 0 <= self.cap <= C.N_ACTIONS - 1:
+            raise ValueError(f"cap {cap}: between 0 and {C.N_ACTIONS - 1}")
+        spec = {k: (dt, (self.rows,)) for k, dt in (("pick", np.uint16), ("score", np.int32), ("value", np.float32),
+                                                    ("count", np.int32), ("nodes", np.uint32))}
+        if self.cap:
+            spec.update(actions=(np.uint16, (self.rows, self.cap)), scores=(np.int32, (self.rows, self.cap)))
+        super().__init__(env, spec)
 
 
 class DeviceIO(_DeviceArrays):

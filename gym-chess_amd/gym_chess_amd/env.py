@@ -25,9 +25,9 @@ import numpy as np
 from . import _lib
 from . import buffers as B
 from . import codec as C
-from .buffers import (DeviceIO, PlanesBuffer, PlayoutBuffer, PriorsBuffer, RowsBuffer, TraceBuffer,  # noqa: F401
-                      _DeviceArrays, _GumbelPolicy, _Staging, c_pointers, fetch_arrays, planes_format, upload,
-                      upload_indices)
+from .buffers import (DeviceIO, MinimaxBuffer, PlanesBuffer, PlayoutBuffer, PriorsBuffer, RowsBuffer,  # noqa: F401
+                      TraceBuffer, _DeviceArrays, _GumbelPolicy, _Staging, c_pointers, fetch_arrays, planes_format,
+                      upload, upload_indices)
 
 REASONS = {0: "none", 1: "mate", 2: "repetition", 3: "move_cap", 4: "no_moves", 5: "both_kings_checked",
            6: "invalid_action", 7: "already_done", 8: "mated_by_opponent", 9: "opponent_no_move",
@@ -44,8 +44,9 @@ class BatchedChessEnv:
         # the uploaded lists of policy_priors (int32 boards), step_boards / encode_planes_rows (int32
         # boards + uint16 actions) and clone_boards (2 x int32 indices); step_boards' own rows buffer
         self._staging = {"priors": _Staging(self, 4), "rows": _Staging(self, 6), "clone": _Staging(self, 8),
-                         "playouts": _Staging(self, 4)}
+                         "playouts": _Staging(self, 4), "minimax": _Staging(self, 4)}
         self._rows_out = None
+        self._minimax_out = None
         ib = None
         if initial_board is not None:
             ib = C.board_to_array(initial_board)
@@ -87,6 +88,10 @@ class BatchedChessEnv:
                 self.synchronize()
                 self._rows_out.close()
                 self._rows_out = None
+            if self._minimax_out is not None:
+                self.synchronize()
+                self._minimax_out.close()
+                self._minimax_out = None
             self._L.gc_env_destroy(self._h)
             self._h = None
 
@@ -581,6 +586,61 @@ class BatchedChessEnv:
             self._playouts = []
         self._playouts.append(weakref.ref(po))
         return po
+
+    # ------------------------------------------------------------------ fixed-depth minimax search
+    MINIMAX_MATE = 30000  # a mate delivered at ply p scores MINIMAX_MATE - p
+
+    def minimax_buffer(self, rows, cap=0):
+        """device memory for minimax: pick uint16[rows], score int32[rows], value float32[rows],
+        count int32[rows], nodes uint32[rows] and, with cap > 0, the root lists actions
+        uint16[rows][cap] / scores int32[rows][cap]"""
+        return MinimaxBuffer(self, rows, cap=cap)
+
+    def minimax(self, boards=None, rows=None, depth=2, seed=None, draw=0, out=None, nodes=False):
+        """A fixed-depth (1..4) minimax search of the listed boards (gc_env_minimax,
+        gym-chess_amd/csrc/gc_minimax.h): ONE launch, asynchronous on the env's stream, that reads
+        the boards' positions and writes nothing of the env.  Row j searches board boards[j] and
+        writes out.pick (the best root move, 0xFFFF without one -- what step_device(actions=...) /
+        step_boards take), out.score (its exact negamax score: material in the step's capture values
+        at the leaves, MINIMAX_MATE - ply for a mate), out.value (+-1 for a mate, else
+        clamp(score, -16, 16) / 16, from the view of the side to move -- what SearchTree.backup
+        takes for a new leaf) and out.count (the root's legal moves); a buffer with cap > 0 also
+        takes the first cap root moves in ascending action id with their exact scores (out.actions
+        / out.scores, padding 0xFFFF / INT32_MIN).  Reference rules; any opponent setting.
+        boards: None = boards 0..rows-1 (rows defaults to out.rows, or N without out); an
+        array-like of board indices (uploaded to a staging buffer of this env on its stream, a
+        synchronous copy as clone_boards') or a device pointer (int) to int32[rows], with rows.
+        Duplicates are fine; an index outside [0, N) gives count -1, a done board count 0, both with
+        pick 0xFFFF, score 0 and value 0.  seed None: ties at the best score go to the lowest action
+        id; a seed: to a uniform draw among them on the stream (seed, board index, draw + i), which
+        consumes as many draws as there are ties.  nodes=True also writes out.nodes (positions
+        visited per row).  out: a minimax_buffer(); None = a buffer this env keeps and grows.
+        Returns the buffer written."""
+        if boards is None:
+            pb, m = None, (out.rows if out is not None else self.num_boards) if rows is None else int(rows)
+        elif isinstance(boards, int):
+            if rows is None:
+                raise ValueError("a device pointer needs rows")
+            pb, m = boards or None, int(rows)
+        else:
+            pb, m = upload_indices(self._staging["minimax"], boards, rows)
+        if out is None:
+            if self._minimax_out is None or m > self._minimax_out.rows:
+                if self._minimax_out is not None:
+                    self.synchronize()
+                    self._minimax_out.close()
+                self._minimax_out = MinimaxBuffer(self, max(256, 1 << max(m - 1, 0).bit_length()))
+            out = self._minimax_out
+        elif not isinstance(out, MinimaxBuffer):
+            raise TypeError("out must be a minimax_buffer()")
+        if m > out.rows:
+            raise ValueError(f"{m} rows, the minimax buffer holds {out.rows}")
+        p = out.ptr
+        _lib.check(self._L.gc_env_minimax(self._h, pb, m, int(depth), int(seed is not None),
+                                          ctypes.c_uint64(0 if seed is None else int(seed)), int(draw) & 0xFFFFFFFF,
+                                          p["pick"], p["score"], p["value"], p["count"], out.cap, p.get("actions"),
+                                          p.get("scores"), p["nodes"] if nodes else None))
+        return out
 
     def stream(self):
         """the env's hipStream_t (for callers ordering their own device work with it)"""

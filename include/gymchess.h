@@ -775,6 +775,55 @@ int gc_playout_destroy(gc_playout* p);
 int gc_playout_run(gc_playout* p, const int32_t* d_board_idx, int rows, int n_plies, uint64_t seed, uint32_t draw,
                    float cut_weight, float* d_value, int32_t* d_tally);
 uint64_t gc_playout_device_bytes(gc_playout* p);
+/* Fixed-depth minimax search (gc_minimax.h): for a device list of boards of `e`, every root move's
+ * exact depth-limited negamax score, the best move and a leaf value -- a network-free move chooser
+ * (a shallow material searcher as an opponent or yardstick), a deterministic leaf evaluator in the
+ * playouts' place, and exact scores to build priors or targets from.  Position-only, on reference
+ * rules: it reads a board's bitboards, side to move and rights and writes nothing of `e`; the
+ * opponent setting and the player colour play no part.  ONE launch, asynchronous on e's stream, no
+ * host synchronisation, no atomics, no device allocation (hence no handle).
+ * The contract, exact and integer.  For a position pos:
+ *   moves(pos)     the engine's legal list (get_possible_moves(state, player)) in ASCENDING ACTION ID.
+ *   child(pos, a)  what the env's step makes of next_state: rights forced as by State::new, check
+ *                  flags set.  An edge on which both kings are in check (step reason 5: the episode
+ *                  ends, nobody is rewarded) is a terminal edge worth 0.  3-fold repetition, the
+ *                  move cap and a full window play no part in the tree.
+ *   V(pos, d, ply) for the side to move, the first rule that applies:
+ *     1. moves(pos) empty: -(MATE - ply) if the side to move is in check, MATE = 30000; else 0.
+ *     2. d == 0: material(pos) = sum over Q 10, R 5, B 3, N 3, P 1 of (own - enemy), UNCLAMPED,
+ *        kings 0 (the step's capture values).  The leaf still counts its moves first (rule 1), so
+ *        a depth-1 search sees a mate in one.
+ *     3. max over a in moves(pos) of E(pos, a, d, ply); E = 0 on a both-checked edge, else
+ *        -V(child(pos, a), d - 1, ply + 1).
+ * At the root, 1 <= depth <= 4, for row j with board b = d_board_idx[j] (NULL: b = j):
+ *   scores   s_a = E(root, a, depth, 0) for every legal a; score = max s_a.
+ *   ties     T = the moves with s_a == score, in ascending action id.
+ *   pick     tiebreak 0 (first): T[0].  tiebreak 1 (random): T[i*], i* the largest i < |T| with
+ *            policy_index(seed, b, draw + i, i + 1) == 0 -- reservoir sampling, uniform over T;
+ *            keyed by the BOARD index b, not the row (gc_env_step_boards' stream); it consumes the
+ *            draws draw .. draw + |T| - 1.
+ *   value    f32: +1.0 if score >= MATE - 128; -1.0 if score <= -(MATE - 128); else
+ *            clamp(score, -16, 16) * 0.0625f -- exact in fp32, on the scale of the playouts'
+ *            material term, from the view of the side to move: what gc_tree_backup's d_value takes.
+ *   count    the number of root moves.
+ *   rows     b outside [0, gc_env_num_boards(e)): count -1, pick 0xFFFF, score 0, value 0.0f.  A
+ *            board whose state is done: count 0 and the same (gc_playout_run skips it the same
+ *            way).  A live root without a move: count 0, pick 0xFFFF, rule 1's score and its
+ *            value.  Duplicated indices are fine; whatever the array holds, every access stays in
+ *            bounds.
+ *   lists    d_actions u16 [rows][cap], d_scores i32 [rows][cap] (either or both, cap >= 1): the
+ *            first min(count, cap) root moves in ascending action id with their EXACT s_a, padded
+ *            with 0xFFFF / INT32_MIN; the whole block is defined after the call.
+ *   d_nodes  u32 [rows]: the positions visited (the root and every position V was taken of; 0 for
+ *            a skipped row) -- what the pruning saved shows against a full-width count.
+ * Pruning is alpha-beta below each root move; every output equals the definition above.  A root
+ * move is cut only once proven strictly below the best so far; with a list asked for, none is.
+ * Any output pointer may be NULL; cap == 0 comes with NULL lists.  rows == 0 succeeds and launches
+ * nothing.  Refused with nothing launched (-1, gc_last_error): a NULL env, rows < 0, depth outside
+ * 1..4, a tiebreak other than 0 / 1, cap < 0, a list with cap == 0, a rules="fide" env. */
+int gc_env_minimax(gc_env* e, const int32_t* d_board_idx, int rows, int depth, int tiebreak, uint64_t seed,
+                   uint32_t draw, uint16_t* d_pick, int32_t* d_score, float* d_value, int32_t* d_count, int cap,
+                   uint16_t* d_actions, int32_t* d_scores, uint32_t* d_nodes);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
