@@ -29,6 +29,17 @@
 // the maximum, the ties in rank order, the reservoir rule.  LDS: one SCRATCH_SLOTS x 64 x 8 B plane
 // per interior level below the root, three (24 KB) at depth 4.  The wave lasts as long as its
 // slowest lane, and 64 rows are 64 waves; splitting one root move's subtree over lanes is not done.
+//
+// Quiescence (gc_env_minimax_q, quiesce = q in 1..MM_MAX_QUIESCE).  The leaf's material becomes
+// QS(pos, q, ply): no move: rule 1; q == 0: material; in check: the maximum over ALL moves, no
+// stand-pat; else max(material, the maximum over the captures) -- each edge EQ = 0 when both kings
+// are checked, else -QS(child, q - 1, ply + 1).  The levels object carries q (MmQuiesce<L>): with
+// it mm_node<0> enters mm_qs, a fixed nest of MM_MAX_QUIESCE levels with the remaining q a runtime
+// value; without it (quiesce == 0) nothing of this is instantiated.  A quiescence level parks no move
+// set: it walks the own pieces by ctz and takes legal_targets per piece (select_action's ms.big
+// walk), masked with g.opp unless in check, then the castles when in check -- no LDS of its own.
+// Order: ascending action id, as everywhere else here; fail-soft alpha-beta, the stand-pat value
+// raises alpha and returns at once when it reaches beta.
 #pragma once
 
 namespace gc {
@@ -37,6 +48,7 @@ static constexpr int MM_MATE = 30000;      // a mate at ply p scores MM_MATE - p
 static constexpr int MM_MATE_BAND = 128;   // scores within it of MM_MATE are mates (value +-1)
 static constexpr int MM_INF = 32767;       // outside every score
 static constexpr int MM_MAX_DEPTH = 4;
+static constexpr int MM_MAX_QUIESCE = 4;   // quiescence plies below a leaf (0: the leaf is its material)
 static constexpr int MM_LANES = 64;        // root moves are dealt to this many lanes, rank % MM_LANES
 
 // material from the view of the side to move: sum of value * (own - enemy) in apply_move's capture
@@ -67,6 +79,89 @@ GC_HD bool minimax_tie_keeps(u64 seed, u32 board, u32 draw, u32 i) {
 // (4096 / 4098) sorts before the queen side (4097 / 4099), so with both the two swap
 GC_HD int mm_ascending(int action, u32 castles) { return (action >= 4096 && castles == 3u) ? action ^ 1 : action; }
 
+// the levels object of a search with quiescence: L's planes and the plies q below a leaf
+template <class L>
+struct MmQuiesce {
+    L& lv;
+    int q;
+    template <int D>
+    GC_HDM decltype(auto) at() { return lv.template at<D>(); }
+};
+template <class L> struct mm_quiesces { static constexpr bool value = false; };
+template <class L> struct mm_quiesces<MmQuiesce<L>> { static constexpr bool value = true; };
+
+template <int N, bool PRUNE>
+GC_HD int mm_qs(const Pos& s, const Gen& g, int q, int ply, int alpha, int beta, u32& nodes);
+
+// EQ(s, a, q, ply) within (alpha, beta), q >= 1 the quiescence plies left at s, N >= q the levels
+// left in the nest: mm_edge with QS below it
+template <int N, bool PRUNE>
+GC_HD int mm_qedge(const Pos& s, bool white, int action, int q, int ply, int alpha, int beta, u32& nodes) {
+    Pos c = s;
+    c.meta = (c.meta & ~(u32)M_RIGHTS) | eff_rights(s);
+    int rw;
+    bool irrev;
+    apply_legal(c, white, action, &rw, &irrev);
+    Gen g;
+    gen_init(c, g);
+    if (g.in_check && mover_checked(s, c, white, action)) return 0;
+    nodes++;
+    return -mm_qs<N - 1, PRUNE>(c, g, q - 1, ply + 1, -beta, -alpha, nodes);
+}
+
+// QS(s, q, ply) within (alpha, beta); g = gen_init(s), q <= N.  The caller has counted the node.
+// One call site of mm_qedge per level (the castles ride in the same loop as the piece moves): the
+// nest is inlined, so a second one would double the code at every level.
+template <int N, bool PRUNE>
+GC_HD int mm_qs(const Pos& s, const Gen& g, int q, int ply, int alpha, int beta, u32& nodes) {
+    if (count_moves(s, g) == 0) return g.in_check ? -(MM_MATE - ply) : 0;
+    const int stand = minimax_material(s);
+    if constexpr (N == 0) {
+        return stand;
+    } else {
+        if (q <= 0) return stand;
+        int best = -MM_INF;
+        if (!g.in_check) {  // the stand-pat: the side to move may decline every capture
+            best = stand;
+            if (PRUNE) {
+                alpha = best > alpha ? best : alpha;
+                if (alpha >= beta) return best;
+            }
+        }
+        const u64 keep = g.in_check ? ~0ull : g.opp;  // in check every evasion, else the captures
+        u32 cs = g.in_check ? g.castles : 0u;
+        u64 pcs = g.own, tg = 0;
+        int sq = 0;
+        for (;;) {  // ascending action id: squares by ctz, targets by ctz, then KS, QS
+            while (!tg && pcs) {
+                sq = ctz(pcs);
+                pcs &= pcs - 1;
+                tg = legal_targets(s, g, sq, type_at(s, sq)) & keep;
+            }
+            int a;
+            if (tg) {
+                a = sq * 64 + ctz(tg);
+                tg &= tg - 1;
+            } else if (cs & 2u) {
+                a = g.white ? A_KSW : A_KSB;
+                cs &= ~2u;
+            } else if (cs & 1u) {
+                a = g.white ? A_QSW : A_QSB;
+                cs = 0u;
+            } else {
+                break;
+            }
+            const int e = mm_qedge<N, PRUNE>(s, g.white, a, q, ply, alpha, beta, nodes);
+            best = e > best ? e : best;
+            if (PRUNE) {
+                alpha = best > alpha ? best : alpha;
+                if (alpha >= beta) break;
+            }
+        }
+        return best;
+    }
+}
+
 template <int D, bool PRUNE, class L>
 GC_HD int mm_node(const Pos& s, const Gen& g, int ply, int alpha, int beta, L& lv, u32& nodes);
 
@@ -89,7 +184,9 @@ GC_HD int mm_edge(const Pos& s, bool white, int action, int ply, int alpha, int 
 template <int D, bool PRUNE, class L>
 GC_HD int mm_node(const Pos& s, const Gen& g, int ply, int alpha, int beta, L& lv, u32& nodes) {
     nodes++;
-    if constexpr (D == 0) {
+    if constexpr (D == 0 && mm_quiesces<L>::value) {
+        return mm_qs<MM_MAX_QUIESCE, PRUNE>(s, g, lv.q, ply, alpha, beta, nodes);
+    } else if constexpr (D == 0) {
         if (count_moves(s, g) == 0) return g.in_check ? -(MM_MATE - ply) : 0;
         return minimax_material(s);
     } else {
@@ -242,10 +339,18 @@ struct MinimaxArgs {
     int cap;
     uint16_t* actions;   // [rows][cap] or null
     int32_t* scores;     // [rows][cap] or null
+    int quiesce;         // 0 .. MM_MAX_QUIESCE; read by the QUIESCE instantiations only
 };
 
-// NODES: count the positions visited (nodes_out is not null)
-template <bool NODES>
+template <bool QUIESCE>
+__device__ __forceinline__ auto& mm_levels_of(MmLevels& plain, gc::MmQuiesce<MmLevels>& q) {
+    if constexpr (QUIESCE) return q;
+    else return plain;
+}
+
+// NODES: count the positions visited (nodes_out is not null); QUIESCE: a quiescence search below
+// the leaves (a.quiesce >= 1; the levels object is MmQuiesce<MmLevels>)
+template <bool NODES, bool QUIESCE = false>
 __global__ void __launch_bounds__(MINIMAX_BLOCK) k_minimax(SoA st, MinimaxArgs a, u32* __restrict__ nodes_out) {
     __shared__ u64 lds_levels[(gc::MM_MAX_DEPTH - 1) * SCRATCH_SLOTS * MINIMAX_BLOCK];
     __shared__ u64 lds_root[SCRATCH_SLOTS];
@@ -274,7 +379,9 @@ __global__ void __launch_bounds__(MINIMAX_BLOCK) k_minimax(SoA st, MinimaxArgs a
     u32 nodes = 0;
     if (live && count == 0) score = g.in_check ? -gc::MM_MATE : 0;
     if (live && count > 0) {
-        MmLevels lv{lds_levels + lane};
+        MmLevels planes{lds_levels + lane};
+        gc::MmQuiesce<MmLevels> deeper{planes, a.quiesce};
+        auto& lv = mm_levels_of<QUIESCE>(planes, deeper);
         const bool exact = acts || scs;
         gc::MinimaxLane ln = {-gc::MM_INF, 0u};
         for (int k = lane; k < count; k += MINIMAX_BLOCK) {

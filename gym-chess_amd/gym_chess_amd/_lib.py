@@ -127,6 +127,7 @@ SIGNATURES = {
     "gc_playout_run": (_I, [_P, _P, _I, _I, _U64, ctypes.c_uint32, ctypes.c_float, _P, _P]),
     "gc_playout_device_bytes": (_U64, [_P]),
     "gc_env_minimax": (_I, [_P, _P, _I, _I, _I, _U64, ctypes.c_uint32, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "gc_env_minimax_q": (_I, [_P, _P, _I, _I, _I, _I, _U64, ctypes.c_uint32, _P, _P, _P, _P, _I, _P, _P, _P]),
     "gc_env_get_stream": (_I, [_P, _P]),
     "gc_device_alloc": (_I, [_I, _U64, _P]),
     "gc_device_free": (_I, [_I, _P]),

@@ -596,8 +596,8 @@ class BatchedChessEnv:
         uint16[rows][cap] / scores int32[rows][cap]"""
         return MinimaxBuffer(self, rows, cap=cap)
 
-    def minimax(self, boards=None, rows=None, depth=2, seed=None, draw=0, out=None, nodes=False):
-        """A fixed-depth (1..4) minimax search of the listed boards (gc_env_minimax,
+    def minimax(self, boards=None, rows=None, depth=2, seed=None, draw=0, out=None, nodes=False, quiesce=0):
+        """A fixed-depth (1..4) minimax search of the listed boards (gc_env_minimax_q,
         gym-chess_amd/csrc/gc_minimax.h): ONE launch, asynchronous on the env's stream, that reads
         the boards' positions and writes nothing of the env.  Row j searches board boards[j] and
         writes out.pick (the best root move, 0xFFFF without one -- what step_device(actions=...) /
@@ -615,6 +615,12 @@ class BatchedChessEnv:
         id; a seed: to a uniform draw among them on the stream (seed, board index, draw + i), which
         consumes as many draws as there are ties.  nodes=True also writes out.nodes (positions
         visited per row).  out: a minimax_buffer(); None = a buffer this env keeps and grows.
+        quiesce (0..4): 0 = the leaf is its material (the default, the plain search and its
+        kernels).  q > 0 = a quiescence search of up to q more plies in the leaf's place: a leaf in
+        check takes the best of ALL its moves, any other the better of its material (standing pat)
+        and its best capture (a move onto an enemy piece; castles and quiet promotions are none),
+        each followed the same way with q - 1; mates found there score MINIMAX_MATE - ply as above.
+        A depth-1 / depth-2 search stops taking defended pieces with it; quiesce=2..4 for a match.
         Returns the buffer written."""
         if boards is None:
             pb, m = None, (out.rows if out is not None else self.num_boards) if rows is None else int(rows)
@@ -636,10 +642,10 @@ class BatchedChessEnv:
         if m > out.rows:
             raise ValueError(f"{m} rows, the minimax buffer holds {out.rows}")
         p = out.ptr
-        _lib.check(self._L.gc_env_minimax(self._h, pb, m, int(depth), int(seed is not None),
-                                          ctypes.c_uint64(0 if seed is None else int(seed)), int(draw) & 0xFFFFFFFF,
-                                          p["pick"], p["score"], p["value"], p["count"], out.cap, p.get("actions"),
-                                          p.get("scores"), p["nodes"] if nodes else None))
+        _lib.check(self._L.gc_env_minimax_q(self._h, pb, m, int(depth), int(quiesce), int(seed is not None),
+                                            ctypes.c_uint64(0 if seed is None else int(seed)), int(draw) & 0xFFFFFFFF,
+                                            p["pick"], p["score"], p["value"], p["count"], out.cap, p.get("actions"),
+                                            p.get("scores"), p["nodes"] if nodes else None))
         return out
 
     def stream(self):

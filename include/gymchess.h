@@ -824,6 +824,29 @@ uint64_t gc_playout_device_bytes(gc_playout* p);
 int gc_env_minimax(gc_env* e, const int32_t* d_board_idx, int rows, int depth, int tiebreak, uint64_t seed,
                    uint32_t draw, uint16_t* d_pick, int32_t* d_score, float* d_value, int32_t* d_count, int cap,
                    uint16_t* d_actions, int32_t* d_scores, uint32_t* d_nodes);
+/* The same search with a quiescence search at the leaves: gc_env_minimax's arguments with `quiesce`
+ * after `depth`, 0 <= quiesce <= 4 (MM_MAX_QUIESCE).  quiesce == 0 IS gc_env_minimax: the same launch
+ * of the same kernels.  With quiesce = q > 0 only rule 2 of V changes: at d == 0 the value is
+ * QS(pos, q, ply), for the side to move the first rule that applies:
+ *     1. moves(pos) empty: -(MATE - ply) if the side to move is in check, else 0 (rule 1 above).
+ *     2. q == 0: material(pos).
+ *     3. the side to move is in check (the flag rule 1 uses): no stand-pat; the max over ALL a in
+ *        moves(pos) of EQ(pos, a, q, ply).
+ *     4. max(material(pos), max over the CAPTURES a in moves(pos) of EQ(pos, a, q, ply)).  A capture
+ *        is a legal move a < 4096 whose target square holds an enemy piece before the move -- under
+ *        the reference rules that includes an enemy king, worth 0.  Castles and pawn pushes to the
+ *        last rank are not captures.
+ *   EQ = 0 on a both-checked edge, as E; else -QS(child(pos, a), q - 1, ply + 1), the same child.
+ * Everything above the leaves is as stated for gc_env_minimax: the root scores, the ties, the pick
+ * under both tie rules, value's mapping, count, the lists, the skipped rows.  d_nodes counts every
+ * position QS is taken of as well.  depth + quiesce <= 8 keeps ply far below the 128-wide mate band.
+ * Pruning: QS is fail-soft alpha-beta too; the stand-pat value raises alpha and returns at once when
+ * it reaches beta; captures are tried in ascending action id.  Every output equals the definition.
+ * Refused with nothing launched: everything gc_env_minimax refuses (a rules="fide" env included)
+ * and quiesce outside 0..4. */
+int gc_env_minimax_q(gc_env* e, const int32_t* d_board_idx, int rows, int depth, int quiesce, int tiebreak,
+                     uint64_t seed, uint32_t draw, uint16_t* d_pick, int32_t* d_score, float* d_value,
+                     int32_t* d_count, int cap, uint16_t* d_actions, int32_t* d_scores, uint32_t* d_nodes);
 int gc_env_get_stream(gc_env* e, void** stream);
 /* device memory helpers for callers without an allocator; kind 0 h2h 1 h2d 2 d2h 3 d2d
  * (synchronous on the env's stream) */
