@@ -1400,26 +1400,41 @@ GC_HD int select_action_swar(const Pos& s, const Gen& g, const MoveSet& ms, cons
 // origin of target `to` of set j.  Leapers: origin = to + a signed byte of four packed words
 // (pawn offsets by colour); sliders: the nearest occupied square behind the target on the
 // set's line (the squares between are empty: the ray came through them), branch-free.
+GC_HD u64 brev64(u64 x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __brevll(x);
+#else
+    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0F0F0F0F0F0F0F0Full) | ((x & 0x0F0F0F0F0F0F0F0Full) << 4);
+    return __builtin_bswap64(x);
+#endif
+}
+// Straight-line, and short behind the target: what depends on the set alone -- the offset word,
+// the stride's constant, the occupancy's orientation -- is made beside the set's fetch.
 GC_HD int sw_origin(const Gen& g, int j, int to) {
-    const u64 w0 = g.white ? pack8(8, 16, 7, 9, -15, -17, 17, 15) : pack8(-8, -16, -9, -7, -15, -17, 17, 15);
-    const u64 w1 = pack8(-6, -10, 10, 6, 0, 0, 0, 0), w2 = pack8(0, 0, 0, 0, 8, -8, 1, -1);
-    const u64 w3 = pack8(9, 7, -7, -9, 0, 0, 0, 0);
-    const int q = j >> 3;
-    const u64 w = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : w3;
-    const int off = (int)(signed char)(w >> (8 * (j & 7)));
-    // sliders: direction d = j - SW_ORTH; d 1, 2, 6, 7 move toward higher squares
-    const int d = (j - SW_ORTH) & 7;
-    const bool up = ((0xC6u >> d) & 1) != 0;
+    // Leapers.  The pawn, knight and king sets start at 0, 4 and 20, so set j's offset is byte
+    // (j + 4) & 7 of its kind's word (the pawns' in the upper half, by colour): one word chosen
+    // by the set's range, one shift.
+    const u32 pw = g.white ? (u32)(pack8(0, 0, 0, 0, 8, 16, 7, 9) >> 32) : (u32)(pack8(0, 0, 0, 0, -8, -16, -9, -7) >> 32);
+    const u64 nw = pack8(-15, -17, 17, 15, -6, -10, 10, 6), kw = pack8(8, -8, 1, -1, 9, 7, -7, -9);
+    const u32 d = ((u32)j + 4u) & 7u;
+    const u64 w = j < SW_N ? (u64)pw << 32 : j < SW_ORTH ? nw : kw;
+    const int off = (int)(signed char)(w >> (8 * d));
+    // Sliders: d is the direction as well (j - SW_ORTH); d 1, 2, 6, 7 move toward higher squares.
     // The squares behind the target at the line's stride (8, 1, 9, 7), not clipped to the board's
-    // edge: one periodic constant per stride, without the target's own bit, shifted once to end
-    // (toward lower squares) or start (toward higher ones) beside the target.  The ray came
-    // through empty squares, so the nearest occupied square at that stride is the origin, and a
-    // square where the stride wraps over an edge lies beyond it.
+    // edge: one periodic constant per stride, without the target's own bit, shifted once to start
+    // beside the target.  The ray came through empty squares, so the nearest occupied square at
+    // that stride is the origin, and a square where the stride wraps over an edge lies beyond it.
+    // Toward higher squares the origin lies below the target: the same on the bit-reversed board
+    // (each constant's mirror image is the constant of the opposite direction), where the target
+    // is square 63 - to and the origin 63 - the lowest set bit.
+    const u32 flip = ((0xC6u >> d) & 1u) ? 63u : 0u;
     const bool file = d < 2, row = d < 4, dg = d == 5 || d == 6;
-    const u64 pl = file ? 0x0080808080808080ull : row ? 0x7FFFFFFFFFFFFFFFull : dg ? 0x0040201008040201ull : 0x0102040810204081ull;
     const u64 ph = file ? 0x0101010101010100ull : row ? 0xFFFFFFFFFFFFFFFEull : dg ? 0x8040201008040200ull : 0x8102040810204080ull;
-    const u64 x = g.occ & (up ? pl >> (63 - to) : ph << to);
-    const int sl = x ? (up ? msb(x) : ctz(x)) : 0;
+    const u64 o = flip ? brev64(g.occ) : g.occ;
+    const u64 x = o & (ph << ((u32)to ^ flip));
+    const int sl = x ? (int)((u32)ctz(x | (1ull << 63)) ^ flip) : 0;
     const bool slider = j >= SW_ORTH && j < SW_K;
     return slider ? sl : to + off;
 }
@@ -1465,15 +1480,56 @@ GC_HD u64 byte_prefix(u64 w) {  // inclusive prefix sums of the 8 bytes (no byte
 // the fused ply's makers each hand over the prefixes of their own counts)
 GC_HD int sw_locate_pre(const u64* pw, int& k) {
     const u64 p0 = pw[0], p1 = pw[1], p2 = pw[2], p3 = pw[3];
-    const int c1 = (int)(p0 >> 56), c2 = c1 + (int)(p1 >> 56), c3 = c2 + (int)(p2 >> 56);
-    const int w = (k >= c1) + (k >= c2) + (k >= c3);
+    // (unsigned throughout: the rank is never negative, and the device then needs no sign extension)
+    const u32 c1 = (u32)(p0 >> 56), c2 = c1 + (u32)(p1 >> 56), c3 = c2 + (u32)(p2 >> 56);
+    const u32 uk = (u32)k;
+    const u32 w = (uk >= c1 ? 1u : 0u) + (uk >= c2 ? 1u : 0u) + (uk >= c3 ? 1u : 0u);
     const u64 p = w == 0 ? p0 : w == 1 ? p1 : w == 2 ? p2 : p3;
-    k -= w == 0 ? 0 : w == 1 ? c1 : w == 2 ? c2 : c3;
-    const u64 H = 0x8000800080008000ull, K = (u64)(k + 1) * 0x0001000100010001ull, M = 0x00FF00FF00FF00FFull;
-    const int above = popc((((p & M) | H) - K) & H) + popc(((((p >> 8) & M) | H) - K) & H);
-    const int b = 8 - above;  // bytes with prefix <= k: the set is the next one
-    k -= b ? (int)((p >> (8 * b - 8)) & 0xFF) : 0;
-    return 8 * w + b;
+    u32 r = uk - (w == 0 ? 0u : w == 1 ? c1 : w == 2 ? c2 : c3);
+    // (r + 1 <= 255 and every 16-bit lane holds 0x8000 | a byte, so no lane borrows from the
+    // next: the compare runs on the word's halves with one 32-bit K, no multiply)
+    const u32 H = 0x80008000u, K = (r + 1u) | ((r + 1u) << 16), M = 0x00FF00FFu;
+    const u32 pl = (u32)p, ph = (u32)(p >> 32);
+    const u32 above = (u32)__builtin_popcount((((pl & M) | H) - K) & H) + (u32)__builtin_popcount(((((pl >> 8) & M) | H) - K) & H) +
+                      (u32)__builtin_popcount((((ph & M) | H) - K) & H) + (u32)__builtin_popcount(((((ph >> 8) & M) | H) - K) & H);
+    const u32 b = 8u - above;  // bytes with prefix <= k: the set is the next one
+    r -= b ? (u32)((p >> (8u * b - 8u)) & 0xFFu) : 0u;
+    k = (int)r;
+    return (int)(8u * w + b);
+}
+// The same prefix words made directly, for a maker that owns the sets of OWN (a bit per set;
+// the fused ply's three makers below): the running sum rides through the popcounts (the
+// device's popcount adds to an operand) and goes into its byte as it stands, so a word's prefix
+// needs no pass of its own.  A word's sum restarts at each word; the bytes before a maker's
+// first set hold 0 and those after its last one the word's total, as byte_prefix of its packed
+// counts would.  t: the sets by index (only those of OWN are read); part: the maker's total.
+enum : u32 { SW_OWN_Q0 = 0x0000FFFu, SW_OWN_Q2 = 0xFF0F000u, SW_OWN_Q3 = 0x00F0000u };
+template <u32 OWN>
+GC_HD void sw_prefix_make(const u64* t, u64* pw, u32& part) {
+    part = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        u32 run = 0, h[2] = {0, 0};
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const int j = 8 * w + b;
+            if (j < SW_SETS && ((OWN >> j) & 1u)) {
+                // (each sum pinned on the device: left alone the compiler counts both halves from
+                // zero and joins them with a third instruction)
+                run += (u32)__builtin_popcount((u32)t[j]);
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm("" : "+v"(run));
+#endif
+                run += (u32)__builtin_popcount((u32)(t[j] >> 32));
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm("" : "+v"(run));
+#endif
+            }
+            h[b >> 2] |= run << (8 * (b & 3));
+        }
+        pw[w] = (u64)h[0] | ((u64)h[1] << 32);
+        part += run;
+    }
 }
 GC_HD int sw_locate(const u64* cw, int& k) {
     const u64 pw[4] = {byte_prefix(cw[0]), byte_prefix(cw[1]), byte_prefix(cw[2]), byte_prefix(cw[3])};
@@ -1486,6 +1542,37 @@ GC_HD int sw_finish(const Gen& g, int j, u64 tj, int k) {
 GC_HD int sw_castle(const Gen& g, int k) {  // k: the rank among the castles
     if ((g.castles & 1) && k == 0) return g.white ? A_QSW : A_QSB;
     return g.white ? A_KSW : A_KSB;
+}
+// The pick of rank k (< tot, castles counted) from sets fetched one at a time (get(j): the
+// kernels' sit in LDS): the set holding the rank by the byte counts (PRE: cw holds their byte
+// prefixes), then that one set.  More moves than byte sums hold (never in play) take a rolled
+// scan over the sets; any_big says that some board of the wave does (the device passes one
+// wave-level test, so the common path holds no per-lane region), and the located set is made
+// whatever the total: the scan's lanes overwrite it.  For a total of 256 or more the located j
+// and r are garbage by design -- the prefix bytes have overflowed (sw_prefix_make's run << 24
+// wraps in u32, sw_locate_pre's K lanes run together) -- but every index made from them is
+// clamped (w <= 3, b <= 8, j <= SW_SETS - 1) and the scan replaces both before they are used.
+template <bool PRE, class GetSet>
+GC_HD int sw_pick_sets(const GetSet& get, const Gen& g, const u64* cw, int tot, int k, bool any_big) {
+    const int normal = tot - popc(g.castles);
+    int r = k, j = PRE ? sw_locate_pre(cw, r) : sw_locate(cw, r);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(j), "+v"(r));  // (made here: not sunk into a region of the lanes that do not scan)
+#endif
+    if (any_big) {
+        if (tot >= 256) {
+            r = k;
+#pragma unroll 1
+            for (j = 0; j < SW_SETS - 1; j++) {
+                const int c = popc(get(j));
+                if (r < c) break;
+                r -= c;
+            }
+        }
+    }
+    j = j < SW_SETS ? j : SW_SETS - 1;  // a castle's rank runs past the sets
+    const int set_act = sw_finish(g, j, get(j), r);
+    return k >= normal ? sw_castle(g, k - normal) : set_act;
 }
 
 // k-th legal action (0 <= k < ms.total) in reference order, from gen_moves' results

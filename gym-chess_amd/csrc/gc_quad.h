@@ -88,7 +88,8 @@ struct QuadLds {
     u64 enemy[3][QUAD_BOARDS];       // Q2 / Q3 -> Q0, Q2: the enemy map's leaper + orthogonal ([1]), diagonal ([2]) parts
     u32 f1[QUAD_BOARDS];             // Q1 -> Q0: the mover is in check after its move
     // the sets' byte counts (gc_core.h sw_pack: set i in byte i % 8 of word i / 8) reach Q2 as
-    // byte prefixes (byte_prefix) of the words a maker owns; prefixes of disjoint bytes add
+    // byte prefixes of the words a maker owns, made as running sums (sw_prefix_make); prefixes of
+    // disjoint bytes add
     u64 cw3[QUAD_BOARDS];            // Q3 -> Q2: word 2 (the bishop / queen sets)
     u64 cw0[2][QUAD_BOARDS];         // Q0 -> Q2: words 0, 1 (pawns, knights)
     u32 part[4][QUAD_BOARDS];        // partial move totals (Q0's holds the castles)
@@ -123,7 +124,13 @@ struct QuadSetsT {
         for (int j = LO; j < HI; j++) put(j, t[j - LO]);
     }
 };
-using QuadSets = QuadSetsT<QuadLds>;
+// (the API step's makers, ApiQuadVsLds; the rollout's hand over byte prefixes: quad_put below)
+// sets LO .. HI - 1 of t into LDS
+template <int LO, int HI>
+__device__ __forceinline__ void quad_put(QuadLds& L, int l, const u64* t) {
+#pragma unroll
+    for (int j = LO; j < HI; j++) L.sets[j][l] = t[j];
+}
 
 // Q0's choice of the next action, left for the start of the next ply: Q2 makes the pick from
 // the move sets in phase 3 while Q0 and Q1 settle the outcome (the pick was phase 3's longest
@@ -132,8 +139,11 @@ struct QuadPend {
     bool have;     // the move stood: Q2's pick
     uint16_t ra;   // else: the table pick (the launch's first ply: the env's action)
     __device__ int resolve(const QuadLds& L, int l) const {
-        const int pk = (int)L.pick[l];  // read whether taken or not: one ds_read and a select, no exec region
-        return have ? pk : (int)ra;
+        // read whether taken or not: one ds_read and a select (pinned: left to itself the compiler
+        // sinks the read into an exec region of the lanes that take it)
+        u32 pk = L.pick[l];
+        pin(pk);
+        return have ? (int)pk : (int)ra;
     }
 };
 // Q0: what the apply needs of the settled state alone, made at the end of phase 3 and held
@@ -360,22 +370,26 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     const bool opp_chk = g.in_check;
     const bool both = opp_chk && my_chk;  // lib.rs:1442-1446
     const bool gen = mv && !both;
-    QuadSets Q{L, l, {0, 0, 0, 0}, 0};  // sets go to LDS as they are made: no 28-set array held
+    // this maker's sets go to LDS as they are made; their counts leave as the byte prefixes of the
+    // count words (gc_core.h sw_prefix_make: running sums through the popcounts), with the total
+    u64 pw[4] = {0, 0, 0, 0};
+    u32 part = 0;
     int c = 0;
     u32 hl = hl_of(s.meta);
     if (R == 0) {  // pawn sets; castles counted here (phase 2 was Q0's longest: knights to Q3, kings to Q2)
         if (gen) {
             u64 T[SW_SETS];
             sw_pawns(ns, g, T);
-            Q.put_all<SW_P1, SW_N>(T + SW_P1);
+            quad_put<SW_P1, SW_N>(L, l, T);
             // the knight sets here, not on Q3: Q0's SIMDs (Q0 + Q2) are the lighter pair in phase 2
             // (same-box A/B: 14.81 vs 14.59e9 at K = 1 000, 4.62 vs 4.70 us per ply at K = 20)
             sw_knights(ns, g, T);
-            Q.put_all<SW_N, SW_ORTH>(T + SW_N);
-            Q.part += popc(g.castles);
+            quad_put<SW_N, SW_ORTH>(L, l, T);
+            sw_prefix_make<SW_OWN_Q0>(T, pw, part);
+            part += (u32)popc(g.castles);
         }
-        L.cw0[0][l] = byte_prefix(Q.cw[0]);
-        L.cw0[1][l] = byte_prefix(Q.cw[1]);
+        L.cw0[0][l] = pw[0];
+        L.cw0[1][l] = pw[1];
         L.castles[l] = g.castles;
     } else if (R == 1) {
         if (mv && !both) {
@@ -415,21 +429,23 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     } else if (R == 2) {  // unconditional: ignored unless generation is due
         u64 T[SW_SETS];
         sw_orth(ns, g, oc, T);
-        Q.put_all<SW_ORTH, SW_DIAG>(T + SW_ORTH);
+        quad_put<SW_ORTH, SW_DIAG>(L, l, T);
         sw_kings(ns, g, T);
-        Q.put_all<SW_K, SW_SETS>(T + SW_K);
-        L.part[2][l] = (u32)Q.part;
-        // (word 0 holds none of Q2's sets; its own words' prefixes stay in registers across barrier C)
-#pragma unroll
-        for (int k = 1; k < 4; k++) Q.cw[k] = byte_prefix(Q.cw[k]);
+        quad_put<SW_K, SW_SETS>(L, l, T);
+        sw_prefix_make<SW_OWN_Q2>(T, pw, part);
+        L.part[2][l] = part;
+        // (word 0 holds none of Q2's sets; its own words' prefixes stay in registers across barrier
+        // C, pinned: they are complete before it, not made again behind it on the pick's chain)
+        pin(pw[1]); pin(pw[2]); pin(pw[3]);
     } else {
         u64 T[SW_SETS];
         sw_diag(ns, g, dc, T);
-        Q.put_all<SW_DIAG, SW_K>(T + SW_DIAG);
-        L.part[3][l] = (u32)Q.part;
-        L.cw3[l] = byte_prefix(Q.cw[2]);  // its four sets are bytes of word 2
+        quad_put<SW_DIAG, SW_K>(L, l, T);
+        sw_prefix_make<SW_OWN_Q3>(T, pw, part);
+        L.part[3][l] = part;
+        L.cw3[l] = pw[2];  // its four sets are bytes of word 2
     }
-    if (R == 0) L.part[0][l] = (u32)Q.part;
+    if (R == 0) L.part[0][l] = part;
 #ifdef GC_PSTAMPS
     if (R == 1) gc_pst_mark_run(4, pst_loaded);
     else
@@ -445,16 +461,16 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
     if (R == 0) QSETPRIO(0, up);
     if (R == 2) QSETPRIO(2, up);
     if (R == 2) {  // (on Q3, whose SIMDs Q1 shares: 12.77-12.98 vs 13.30-13.42e9)
-        const int total = (int)L.part[0][l] + Q.part + (int)L.part[3][l];
+        const int total = (int)L.part[0][l] + (int)part + (int)L.part[3][l];
         // the words' byte prefixes, summed where two makers meet (word 1: Q0's knights and the
         // rook / queen sets here; word 2: Q3's sets and the king's)
-        const u64 cw[4] = {L.cw0[0][l], Q.cw[1] + L.cw0[1][l], Q.cw[2] + L.cw3[l], Q.cw[3]};
+        const u64 cw[4] = {L.cw0[0][l], pw[1] + L.cw0[1][l], pw[2] + L.cw3[l], pw[3]};
         g.castles = L.castles[l];
         // (a board whose generation is not due reads stale sets here: its pick is not taken)
         L.pick[l] = total > 0 ? (u32)sw_pick_lds<true>(L, l, g, cw, total, (int)scale_rank(L.x0[l], (u32)total)) : (u32)A_NONE;
     }
     if constexpr (CARRY) {
-        const int total = gen ? (R == 0 ? Q.part : (int)L.part[0][l]) + (int)L.part[2][l] + (int)L.part[3][l] : 0;
+        const int total = gen ? (R == 0 ? (int)part : (int)L.part[0][l]) + (int)L.part[2][l] + (int)L.part[3][l] : 0;
         if (R == 0) {
             const u32 rpk = L.rep[l];
             c = (int)(rpk & 0xFFu);
@@ -464,34 +480,27 @@ __device__ __forceinline__ StepOut quad_ply(QuadLds& L, const PairCtx& C, int l,
             if (S0) ra = (uint16_t)L.ra[l];
             h.commit();  // the window write, issued before the outcome
         }
-        bool have = false;
-        if (none) {
-            o.reason = R_NO_MOVES;
-        } else {
-            nst += 1;
-            if (done0) { o.done = 1; o.reason = R_DONE_ALREADY; }
-            else if (cap) { o.done = 1; o.reason = R_MOVE_CAP; }
-            else if (both) { o.done = 1; o.reason = R_BOTH_CHECKED; }
-            else {
-                const u32 chk = white ? ((my_chk ? M_WCHK : 0u) | (opp_chk ? M_BCHK : 0u))
-                                      : ((opp_chk ? M_WCHK : 0u) | (my_chk ? M_BCHK : 0u));
-                s = ns;
-                s.meta = with_hl((ns.meta & ~(u32)(M_WCHK | M_BCHK | M_DONE)) | chk | ((c >= 3 || c == 0) ? M_DONE : 0u), hl);
-                o.reward = -10 + mr;
-                o.moved = 1;
-                if (c >= 3) { o.done = 1; o.reason = R_REPETITION; }  // chess_v2.py:404-407
-                if (c == 0) { o.done = 1; o.reason = R_WINDOW_FULL; }
-                if (total == 0 && opp_chk) {  // 270-272
-                    s.meta |= M_DONE;
-                    o.done = 1;
-                    o.reward += 100;
-                    o.reason = R_MATE;
-                }
-                if (!o.done && !white) s.meta += (1u << M_MC_SHIFT);  // 291-292
-                have = true;
-            }
-            if (o.done) have = false;
-        }
+        // The outcome as flags and selects, no nested regions (in self-play nearly every lane
+        // takes the ladder's last arm, so no branch of it was ever skipped).  Chess_v2.py:245-258
+        // and lib.rs:1442-1446 end the ply before the move stands; where it stands (play) the
+        // 3-fold count, the full window and the mate (270-272) end it after
+        const bool play = !none && !done0 && !cap && !both;
+        const bool rep3 = c >= 3, full = c == 0, mate = total == 0 && opp_chk;  // 404-407
+        const bool end1 = rep3 || full || mate;
+        const u32 chk = white ? ((my_chk ? M_WCHK : 0u) | (opp_chk ? M_BCHK : 0u))
+                              : ((opp_chk ? M_WCHK : 0u) | (my_chk ? M_BCHK : 0u));
+        u32 meta1 = with_hl((ns.meta & ~(u32)(M_WCHK | M_BCHK | M_DONE)) | chk | ((rep3 || full) ? M_DONE : 0u), hl);
+        meta1 |= mate ? (u32)M_DONE : 0u;
+        meta1 += !end1 && !white ? (1u << M_MC_SHIFT) : 0u;  // 291-292
+        const int reason1 = mate ? R_MATE : full ? R_WINDOW_FULL : rep3 ? R_REPETITION : R_NONE;
+        const bool have = play && !end1;
+        nst += none ? 0u : 1u;
+        o.reward = play ? -10 + mr + (mate ? 100 : 0) : 0;
+        o.done = none ? 0 : play ? (end1 ? 1 : 0) : 1;
+        o.reason = none ? R_NO_MOVES : done0 ? R_DONE_ALREADY : cap ? R_MOVE_CAP : both ? R_BOTH_CHECKED : reason1;
+        o.moved = play ? 1 : 0;
+        s = ns;  // (the state is the post-move board or the reset position: nothing else survives a ply)
+        s.meta = meta1;
         if (!have) {  // reset (chess_v2.py:183-206), also the no-move driver reset
             s = L.rp;
             h.bump_gen();

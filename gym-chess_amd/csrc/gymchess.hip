@@ -1340,27 +1340,12 @@ __device__ __forceinline__ Pos pair_settle(const PairHalf& H, bool white) {
     return ns;
 }
 
-// The self-play pick from the move sets in LDS (pair_half with SW): the set holding rank k by
-// the byte counts (gc_core.h sw_locate), then that one set from LDS; more moves than byte sums
-// hold (never in play) take a rolled scan over LDS.  k < tot.
-// (PRE: cw holds the count words' byte prefixes, sw_locate_pre)
+// The self-play pick from the move sets in LDS (pair_half with SW): gc_core.h sw_pick_sets over
+// L.sets, the scan for more moves than byte sums hold (never in play) behind one test of the
+// wave.  k < tot.  (PRE: cw holds the count words' byte prefixes, sw_locate_pre)
 template <bool PRE = false, class LdsT>
 __device__ __forceinline__ int sw_pick_lds(const LdsT& L, int l, const Gen& g, const u64* cw, int tot, int k) {
-    const int normal = tot - popc(g.castles);
-    int r = k, j;
-    if (tot < 256) {
-        j = PRE ? sw_locate_pre(cw, r) : sw_locate(cw, r);
-    } else {
-#pragma unroll 1
-        for (j = 0; j < SW_SETS - 1; j++) {
-            const int c = popc(L.sets[j][l]);
-            if (r < c) break;
-            r -= c;
-        }
-    }
-    j = j < SW_SETS ? j : SW_SETS - 1;  // a castle's rank runs past the sets
-    const int set_act = sw_finish(g, j, L.sets[j][l], r);
-    return k >= normal ? sw_castle(g, k - normal) : set_act;
+    return sw_pick_sets<PRE>([&](int j) { return L.sets[j][l]; }, g, cw, tot, k, __any(tot >= 256) != 0);
 }
 
 // One ply of the paired driver (opponent "none").  In/out: the state s, the action a (picked

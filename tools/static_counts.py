@@ -7,7 +7,9 @@ A role's plies are one loop of four barriers (k_env_rollout4 switches on the rol
 loop stands alone in the listing); a loop is a backward branch and its target, and its segments
 are cut at s_barrier: seg0 runs from the loop's top to the first barrier (the end of phase 0),
 seg1-3 are phases 1-3, the last one runs on into the loop's tail.  Classes: valu (v_*), salu
-(s_*, waits and nops among them), ds, glob (global_ / buffer_), and all of them."""
+(s_*, waits and nops among them), ds, glob (global_ / buffer_), xbr (s_cbranch_execz / execnz:
+the skips of per-lane regions), mul (v_mad_u64_u32, v_mul_*: the slow multiplies among the valu),
+and all of them."""
 import os
 import re
 import subprocess
@@ -77,14 +79,16 @@ def report(name, ins):
             if op == "s_barrier":
                 seg += 1
                 continue
-            c = counts.setdefault(seg, dict(valu=0, salu=0, ds=0, glob=0, all=0))
+            c = counts.setdefault(seg, dict(valu=0, salu=0, ds=0, glob=0, xbr=0, mul=0, all=0))
             k = klass(op)
             if k in c:
                 c[k] += 1
+            c["xbr"] += op.startswith("s_cbranch_exec")
+            c["mul"] += op.startswith(("v_mad_u64_u32", "v_mad_i64_i32", "v_mul_"))
             c["all"] += 1
         for s in sorted(counts):
             c = counts[s]
-            print(f"     seg{s}: valu {c['valu']:4d} salu {c['salu']:4d} ds {c['ds']:3d} glob {c['glob']:3d} all {c['all']}")
+            print(f"     seg{s}: valu {c['valu']:4d} salu {c['salu']:4d} ds {c['ds']:3d} glob {c['glob']:3d} xbr {c['xbr']:2d} mul {c['mul']:2d} all {c['all']}")
 
 
 def main():
